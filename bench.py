@@ -20,6 +20,11 @@ one dof plane (configs 2 and 4), the HDIV z-face dofs (config 3) or -- strips st
 the horizontal edges between two strips (config 5): explicit shared-row lists from the global ids (SharedRowExport).
 `python bench.py --gpus N` without a launcher spawns its own N ranks (torch.distributed.run on 127.0.0.1).
 
+A plain run sets up, warms up, times the K steps and prints the headline figure (`value`, `ms_per_step`).  `--full` adds
+what takes work of its own: the kernel time and roofline figures, config 2's full-kernel comparison in geometry-database
+mode, config 4's fp64 figure and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step computed on
+rank 0 as DIR/<name>.npy (float64; arrays larger than their share of 64 MB as a fixed, seeded sample of their entries).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -107,6 +112,24 @@ def measured_copy_gbs(torch, dev):
     t1.record()
     torch.cuda.synchronize()
     return 5 * 2 * 8 * n / (t0.elapsed_time(t1) * 1e-3) / 1e9
+
+
+DUMP_VALUES = 8_000_000  # float64 values written by --dump-outputs in all: 64 MB
+
+
+def dump_outputs(d, arrays, torch):
+    """Write each output array as d/<name>.npy (float64, flattened).  An array larger than its even share of
+    DUMP_VALUES is written as a sample: the entries at sorted indices drawn with seed 0, the same for the same shape in
+    every run, so that two builds can be compared output for output."""
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_VALUES // len(arrays)
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), share))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(d, name + ".npy"), flat.to(torch.float64).cpu().numpy())
+    log("outputs of the last timed step written to %s: %s" % (d, ", ".join(sorted(arrays))))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -212,7 +235,7 @@ def hdg_state(m, seed):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# workloads: each returns dict(step, kernel_ms, E, b_elem, workload, config, cpu (callable or None), exch)
+# workloads: each returns dict(step, kernel_ms, E, b_elem, workload, config, cpu (callable or None), exch, outputs)
 # ---------------------------------------------------------------------------------------------------------------------
 
 def setup_thermal(args, torch, mrhyde_amd, rank, world, dev):
@@ -306,6 +329,7 @@ def setup_thermal(args, torch, mrhyde_amd, rank, world, dev):
 
     return dict(step=step, kernel_ms=kernel_ms, E=E, b_elem=algorithmic_bytes_per_elem(nn, dim, n), info=info, cpu=cpu,
                 exch=exch, nrows=nrows, nnz=nnz, _blk=blk, _u=u, _res=res, _vals=vals,
+                outputs={"residual": res, "jacobian_values": vals},
                 workload="3D thermal Q%d hex, %d^3 structured mesh per GPU (%s), quadrature %d, volume Jacobian+residual "
                          "assembled into CRS" % (order, nc, args.mesh, qdeg))
 
@@ -409,6 +433,7 @@ def setup_block(kind, args, torch, mrhyde_amd, rank, world, dev):
     wl = ("3D porousMixed (HVOL p + HDIV u), %d^3 hexes per GPU, quadrature 2" % nc if kind == "porous"
           else "3D navierstokes Q2/Q1 hexes, %d^3 per GPU, quadrature 4, no stabilisation" % nc)
     return dict(step=step, kernel_ms=kernel_ms, E=E, b_elem=b_elem, info=info, cpu=cpu, exch=exch, nrows=nrows, nnz=nnz,
+                outputs={"residual": res, "jacobian_values": vals},
                 workload=wl + ", volume Jacobian+residual assembled into CRS")
 
 
@@ -480,6 +505,7 @@ def setup_hdg(args, torch, mrhyde_amd, rank, world, dev):
         return cpu_baseline_hdg(192, 6)  # ~1.5 s of one core per repetition
 
     return dict(step=step, kernel_ms=kernel_ms, E=E, b_elem=11056, info=info, cpu=cpu, exch=exch, nrows=m["ndof"], nnz=plan.nnz,
+                outputs={"schur": S, "gvec": gv, "du": du, "trace_residual": tr_, "trace_values": tv},
                 workload="shallowwaterHybridized HDG on %d^2 quads (Q1 interior, HFACE-1 traces), one backward-Euler stage: side "
                          "blocks + volume + static condensation (fused) + flux->trace scatter" % nc)
 
@@ -499,9 +525,17 @@ def main():
     ap.add_argument("--jacobian", default="database", choices=["database", "full"],
                     help="config 2: 'full' keeps the matrix-core Jacobian kernel on every row block even when the mesh has one "
                          "element geometry (the default replicates one block per assembly pattern then: geometry-database mode)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-sample-layers", type=int, default=0, help="z-layers of the CPU sample of config 2 (0 = all)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure kernel time and roofline figures, config 2's full kernel in "
+                         "geometry-database mode, config 4's fp64 figure and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, at most 64 MB in all "
+                         "(bench_outputs/ in the repository root is git-ignored)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as given: start the N ranks as fresh children (one per GPU, torch.distributed.run on
@@ -569,16 +603,19 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     log("timed %d steps: %.3f s" % (args.steps, elapsed))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, w["outputs"], torch)
     wire = w["exch"].bytes_on_wire() if w["exch"] else 0
     if world > 1:
         tt = torch.tensor([elapsed, float(wire)], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed, wire = float(tt[0].item()), int(tt[1].item())  # (the owner of a shared row -- the lowest rank -- sends nothing)
 
-    # dominant-kernel duration, measured live with HIP events on the context's stream
-    kernel_ms = w["kernel_ms"](max(3, min(args.steps, 10)))
-    b_elem = w["b_elem"]
-    achieved = b_elem * E / (kernel_ms * 1e-3) / 1e9
+    if args.full:
+        # dominant-kernel duration, measured live with HIP events on the context's stream
+        kernel_ms = w["kernel_ms"](max(3, min(args.steps, 10)))
+        b_elem = w["b_elem"]
+        achieved = b_elem * E / (kernel_ms * 1e-3) / 1e9
 
     if rank == 0:
         pname, kern, extra = w["info"]()
@@ -587,7 +624,8 @@ def main():
                "partition": ("strips of element rows, 1 per GPU" if args.config == 5 else "z-slabs, 1 per GPU") if world > 1 else "single block",
                "shared_row_bytes_per_step": wire}
         cfg.update(extra)
-        if args.config == 2 and world == 1 and not args.no_full_compare and str(extra.get("jacobian_mode", "")).startswith("geometry database"):
+        if (args.full and args.config == 2 and world == 1 and not args.no_full_compare
+                and str(extra.get("jacobian_mode", "")).startswith("geometry database")):
             # the same workload with the full kernel, outside the timed region: both numbers in one line
             os.environ["MHA_BP_DATABASE"] = "0"
             w2 = setup_thermal(args, torch, mrhyde_amd, rank, world, dev)
@@ -613,23 +651,24 @@ def main():
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": cfg,
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": None if args.ncell else measured_traffic(args.config, args.mesh, pname),
-                         "kernel_ms": kernel_ms, "bytes_per_elem": b_elem,
-                         "measured_copy_gbs": measured_copy_gbs(torch, dev),
-                         "kernels": kern + " (HIP events around the assembly's kernels on the context's stream)"},
         }
-        if args.config == 4:
-            # the 89-dof element sits above the fp64 balance point, so the engine is also priced against the
-            # fp64 peak.  Algorithmic flops per element of the B^T C B product: per point, P = T_i^T C (n x 16 outputs,
-            # 4 FMAs each) and J += P T_j (n^2 outputs, 4 FMAs each); 27 points, 16 slots; 78.6 TFLOP/s fp64 (matrix =
-            # vector rate on gfx950; profiles/micro/mfma_f64_rate.hip measures 77.6)
-            n_el, nq, ns = 89, 27, 16
-            flops = 2.0 * nq * (n_el * ns * 4 + n_el * n_el * 4)
-            tf = flops * E / (kernel_ms * 1e-3) / 1e12
-            out["roofline"]["fp64"] = {"achieved": tf, "peak": 78.6, "unit": "TFLOP/s", "frac": tf / 78.6,
-                                       "flops_per_elem": flops}
-        out["cpu_baseline"] = None if args.no_cpu_baseline else w["cpu"]()
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": None if args.ncell else measured_traffic(args.config, args.mesh, pname),
+                               "kernel_ms": kernel_ms, "bytes_per_elem": b_elem,
+                               "measured_copy_gbs": measured_copy_gbs(torch, dev),
+                               "kernels": kern + " (HIP events around the assembly's kernels on the context's stream)"}
+            if args.config == 4:
+                # the 89-dof element sits above the fp64 balance point, so the engine is also priced against the
+                # fp64 peak.  Algorithmic flops per element of the B^T C B product: per point, P = T_i^T C (n x 16 outputs,
+                # 4 FMAs each) and J += P T_j (n^2 outputs, 4 FMAs each); 27 points, 16 slots; 78.6 TFLOP/s fp64 (matrix =
+                # vector rate on gfx950; profiles/micro/mfma_f64_rate.hip measures 77.6)
+                n_el, nq, ns = 89, 27, 16
+                flops = 2.0 * nq * (n_el * ns * 4 + n_el * n_el * 4)
+                tf = flops * E / (kernel_ms * 1e-3) / 1e12
+                out["roofline"]["fp64"] = {"achieved": tf, "peak": 78.6, "unit": "TFLOP/s", "frac": tf / 78.6,
+                                           "flops_per_elem": flops}
+            out["cpu_baseline"] = None if args.no_cpu_baseline else w["cpu"]()
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -12,7 +12,7 @@ for r in 1 2 3; do
   for w in 0 1; do
     build $w
     for ov in 1 0; do
-      MHA_K1K2_OVERLAP=$ov timeout -k 10 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline > /tmp/abe.log 2>&1
+      MHA_K1K2_OVERLAP=$ov timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > /tmp/abe.log 2>&1
       echo "round $r DPP=$w overlap=$ov $(tail -1 /tmp/abe.log | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.4f ms/step  kernel_ms %.4f' % (d['ms_per_step'], d['roofline']['kernel_ms']))")"
     done
   done

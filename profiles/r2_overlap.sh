@@ -4,5 +4,5 @@
 set -e
 for ov in 1 0 2 1 0 2; do
   echo "== MHA_K1K2_OVERLAP=$ov"
-  MHA_K1K2_OVERLAP=$ov python bench.py --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('config 2: ms_per_step %.4f kernel_ms %.4f frac %.4f' % (d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['frac']))"
+  MHA_K1K2_OVERLAP=$ov python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('config 2: ms_per_step %.4f kernel_ms %.4f frac %.4f' % (d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline']['frac']))"
 done

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in wg thread; do
   rm -rf /tmp/prof_k1
   if [ $v = thread ]; then export MHA_K1=thread; else unset MHA_K1; fi
-  MHA_K1K2_OVERLAP=0 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_k1 -o p -- python3 $R/bench.py --no-cpu-baseline --steps 20 > /tmp/k1_$v.json 2>/tmp/k1_$v.err
+  MHA_K1K2_OVERLAP=0 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_k1 -o p -- python3 $R/bench.py --full --no-cpu-baseline --steps 20 > /tmp/k1_$v.json 2>/tmp/k1_$v.err
   f=$(find /tmp/prof_k1 -name "*kernel_stats.csv" | head -1)
   python3 - "$f" "$v" /tmp/k1_$v.json <<'PY'
 import csv,sys,json
@@ -16,4 +16,4 @@ print('%-8s K1 %s  K2 %s us  ms_per_step %.4f frac %.3f' % (sys.argv[2], k1, ' +
 PY
 done
 unset MHA_K1
-python3 $R/bench.py --no-cpu-baseline --steps 50 --warmup 10 | tail -c 700
+python3 $R/bench.py --full --no-cpu-baseline --steps 50 --warmup 10 | tail -c 700

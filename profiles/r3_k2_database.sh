@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 for v in 1 0; do
   rm -rf /tmp/prof_db
-  MHA_BP_DATABASE=$v rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_db -o p -- python3 $R/bench.py --no-cpu-baseline --steps 20 > /tmp/db_$v.json 2>/dev/null
+  MHA_BP_DATABASE=$v rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_db -o p -- python3 $R/bench.py --full --no-cpu-baseline --steps 20 > /tmp/db_$v.json 2>/dev/null
   f=$(find /tmp/prof_db -name "*kernel_stats.csv" | head -1)
   python3 - "$f" "$v" /tmp/db_$v.json <<'PY'
 import csv,sys,json

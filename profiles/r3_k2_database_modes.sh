@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp
 IFS=";" read -ra LIST <<< "${MODES:-0 2048;1 2048;2 2048;3 2048;0 1024;0 4096;0 512}"; for v in "${LIST[@]}"; do
   set -- $v
   rm -rf /tmp/prof_db
-  MHA_REP_MODE=$1 MHA_REP_WGS=$2 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_db -o p -- python3 $R/bench.py --no-cpu-baseline --steps 20 > /tmp/db.json 2>/dev/null
+  MHA_REP_MODE=$1 MHA_REP_WGS=$2 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_db -o p -- python3 $R/bench.py --full --no-cpu-baseline --steps 20 > /tmp/db.json 2>/dev/null
   f=$(find /tmp/prof_db -name "*kernel_stats.csv" | head -1)
   python3 - "$f" "$1 wgs $2" /tmp/db.json <<'PY'
 import csv,sys,json
