@@ -428,6 +428,45 @@ def block_patterns_host_apply(dim, nodes, lids, nrows, rowptr, colind, khat, fac
     return vals, tuple(counts)
 
 
+
+def copy_plan_host_apply(nnz, runs, vals):
+    """Host-only test hook: the database modes' line-aligned copy plan of `runs` [n][3] = (source, destination, length)
+    inside vals[0, nnz), applied on the host as the copy kernel's lanes apply it.  `vals` (float64, at least nnz long)
+    is updated in place.  -> (stores [nnz rounded up to whole spans]: entries stored per position,
+    dict(items, segments, max_item_segments, span_entries, segment_registers))."""
+    lib = load_library()
+    runs = _np(np.asarray(runs, np.int64).reshape(-1, 3), np.int64)
+    assert vals.dtype == np.float64 and vals.flags.c_contiguous and len(vals) >= nnz
+    stores = np.zeros(int(nnz) + 4096, np.int32)
+    counts = (C.c_int * 5)()
+    f = lib.mha_test_copy_plan_host_apply
+    f.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    _check(f(int(nnz), runs.shape[0], runs.ctypes.data_as(C.c_void_p), vals.ctypes.data_as(C.c_void_p),
+             stores.ctypes.data_as(C.c_void_p), len(stores), counts))
+    return stores, dict(zip(("items", "segments", "max_item_segments", "span_entries", "segment_registers"), counts))
+
+
+def block_pattern_copy_plan(dim, nodes, lids, nrows, rowptr, colind, khat, factors, fixed=None, chunk_elems=16,
+                            num_cus=8, max_patterns=256):
+    """Host-only test hook: the geometry-database mode of the block-pattern plan on the host.  -> (vals_full: every
+    row block assembled, vals_db: NaN but for the representatives' entries, then the copy plan applied, stores, dict)."""
+    lib = load_library()
+    nodes, lids, rowptr, colind = _np(nodes, np.float64), _np(lids, np.int32), _np(rowptr, np.int32), _np(colind, np.int32)
+    khat, factors = _np(khat, np.float64), _np(factors, np.float64)
+    fx = None if fixed is None else _np(fixed, np.uint8)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    nsym = khat.shape[0] - 1
+    full, db = np.full(len(colind), np.nan), np.full(len(colind), np.nan)
+    stores = np.zeros(len(colind) + 4096, np.int32)
+    counts = (C.c_int * 7)()
+    f = lib.mha_test_block_pattern_copy_plan
+    f.argtypes = [C.c_int] * 6 + [C.c_void_p] * 7 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p]
+    _check(f(int(dim), int(nrows), lids.shape[0], nodes.shape[1], lids.shape[1], nsym, vp(nodes), vp(lids), vp(rowptr),
+             vp(colind), vp(fx), vp(khat), vp(factors), int(chunk_elems), int(num_cus), int(max_patterns), vp(full),
+             vp(db), vp(stores), len(stores), counts))
+    return full, db, stores, dict(zip(("items", "segments", "max_item_segments", "span_entries", "segment_registers",
+                                       "runs", "roles"), counts))
+
 def row_partition(dim, nodes, lids, nrows, rowptr, caps=None):
     """Host-only: the row-owner partition (mha_row_partition_*).  -> dict(row_ptr, rows, elem_ptr, elems, max_*)."""
     lib = load_library()

@@ -307,25 +307,20 @@ bool AssemblyManager::porousDatabaseUsable() {
     const bool is_rep = h_rowptr_[r] >= rep_entry[c] && h_rowptr_[r] < rep_entry[c] + K_of[c] * len_of[c];
     if (!is_rep) replicated[r] = 1;
   }
-  // chunks of the replicated ranges (maximal runs of replicated rows of one class), 1 KB on 128-byte lines
-  std::vector<int32_t> chunks;
+  // copy runs of the replicated ranges (maximal runs of replicated rows of one class): the class's K representative
+  // rows repeat with period len, so every K * len entries of a range read the representatives from their first entry
+  std::vector<CopyRun> runs;
   int64_t computed = 0;
   for (int r = 0; r < nrows_;) {
     if (!replicated[r]) { ++computed; ++r; continue; }
     int r1 = r + 1;
     while (r1 < nrows_ && replicated[r1] && cls[r1] == cls[r]) ++r1;
-    const int c = cls[r], len = len_of[c];
-    const int64_t dbeg = h_rowptr_[r], dend = h_rowptr_[r1];
-    for (int64_t c0 = dbeg / 16 * 16; c0 < dend; c0 += 128) {
-      const int64_t ph = ((c0 - dbeg) % len + len) % len;
-      chunks.push_back(static_cast<int32_t>(c0 / 2));
-      chunks.push_back(static_cast<int32_t>(rep_entry[c] + ph));
-      chunks.push_back(static_cast<int32_t>(dbeg));
-      chunks.push_back(static_cast<int32_t>(dend));
-    }
+    const int c = cls[r];
+    const int64_t dbeg = h_rowptr_[r], dend = h_rowptr_[r1], period = static_cast<int64_t>(K_of[c]) * len_of[c];
+    for (int64_t d0 = dbeg; d0 < dend; d0 += period) runs.push_back({rep_entry[c], d0, std::min(period, dend - d0)});
     r = r1;
   }
-  if (chunks.empty()) { db.why = "no class has a run long enough to replicate"; return false; }
+  if (runs.empty()) { db.why = "no class has a run long enough to replicate"; return false; }
   // elements incident to computed rows store their entries; diagonal positions of the computed face rows only
   std::vector<uint8_t> jacflag(nelem_, 0);
   std::vector<int32_t> diag(nrows_, -1);
@@ -347,18 +342,26 @@ bool AssemblyManager::porousDatabaseUsable() {
     db.elist.upload(elist);
   }
   db.diag.upload(diag);
-  db.chunks.upload(chunks);
-  db.num_chunks = static_cast<int>(chunks.size() / 4);
+  const CopyPlan cp = build_copy_plan(std::move(runs), h_rowptr_[nrows_]);
+  db.copy_items.upload(cp.item);
+  db.copy_segs.upload(cp.seg);
+  db.num_items = cp.num_items();
+  db.num_segs = cp.num_segs();
   db.num_classes = nc;
   db.computed_rows = computed;
   db.state = 1;
   if (std::getenv("MHA_VERBOSE")) {
     int64_t flagged = 0;
     for (uint8_t f : jacflag) flagged += f;
-    fprintf(stderr, "[mrhyde_amd] porousMixed database mode: %d row classes, %lld of %d rows computed, %lld of %d elements store entries, %d chunks\n",
-            nc, (long long)computed, nrows_, (long long)flagged, nelem_, db.num_chunks);
+    fprintf(stderr, "[mrhyde_amd] porousMixed database mode: %d row classes, %lld of %d rows computed, %lld of %d elements store entries, %d copy spans, %d segments\n",
+            nc, (long long)computed, nrows_, (long long)flagged, nelem_, db.num_items, db.num_segs);
   }
   return true;
+}
+
+void AssemblyManager::launchDatabaseCopy(double *crs_vals) {
+  launch_line_copy(porous_db_.copy_items.data(), porous_db_.num_items, porous_db_.copy_segs.data(), porous_db_.num_segs,
+                   h_rowptr_[nrows_], crs_vals, stream_);
 }
 
 // The direct form of the porousMixed assembly (kernels/porous_element.hip) rests on one property of the mesh: any two
@@ -823,7 +826,10 @@ void AssemblyManager::assembleJacRes(int flags, int path, const double *u, const
               launchPointEngine(compute_jacobian, o, 0, porous_db_.num_listed);
             }
             launch_porous_direct_finish(blockDev(), d_inc_ptr_.data(), porous_db_.diag.data(), o.direct_part, res, o.direct_vals, 1, stream_);
-            launch_replicate_runs(porous_db_.chunks.data(), porous_db_.num_chunks, crs_vals, stream_);
+            // (lines that mix copied and computed entries are stored whole: those lanes store back the bits they read,
+            // written earlier on this stream -- the side stream's element kernel joined above; no other wavefront
+            // writes those lines)
+            launchDatabaseCopy(crs_vals);
             last_porous_direct_ = 2;
             break;
           }
@@ -832,7 +838,7 @@ void AssemblyManager::assembleJacRes(int flags, int path, const double *u, const
           launchPointEngine(compute_jacobian, o, 0, nelem_);
           launch_porous_direct_finish(blockDev(), d_inc_ptr_.data(), pdb ? porous_db_.diag.data() : d_direct_diag_.data(), o.direct_part,
                                       res, o.direct_vals, overwrite ? 1 : 0, stream_);
-          if (pdb) launch_replicate_runs(porous_db_.chunks.data(), porous_db_.num_chunks, crs_vals, stream_);
+          if (pdb) launchDatabaseCopy(crs_vals);  // (in-place lanes: as above, every writer ran earlier on stream_)
           last_porous_direct_ = pdb ? 2 : 1;
           break;
         }
@@ -2182,37 +2188,19 @@ void AssemblyManager::prepareBlockPattern() {
   const char *dbm = std::getenv("MHA_BP_DATABASE");
   if (ro_.num_shapes == 1 && !d.has_image && !(dbm && dbm[0] == '0')) {
     std::vector<int32_t> rseg(static_cast<size_t>(h.num_roles) * 4, 0), rptr(static_cast<size_t>(h.num_roles) + 1, 0);
-    struct Run { int32_t src, dst, len; };
-    std::vector<Run> runs;
     for (int k = 0; k < h.num_roles; ++k) {
       rseg[4 * k] = k;
       rseg[4 * k + 1] = 0;
       rseg[4 * k + 2] = 1;
       rptr[k + 1] = k + 1;
-      const int32_t *ro = &h.role[static_cast<size_t>(k) * kBpRoleInts];
-      const int64_t row_base = (static_cast<int64_t>(ro[4]) << 32) | static_cast<uint32_t>(ro[3]);  // R_ROWB_HI / _LO
-      const int nruns = ro[5], nblocks = ro[6];                                                        // R_NRUNS, R_NBLOCKS
-      const int32_t *rl = &h.runlen[static_cast<size_t>(h.role_runlen_off[k])];
-      for (int j = 1; j < nblocks; ++j)
-        for (int r = 0; r < nruns; ++r)
-          runs.push_back({h.rowbase[static_cast<size_t>(row_base + r)], h.rowbase[static_cast<size_t>(row_base + static_cast<int64_t>(j) * nruns + r)], rl[r]});
     }
-    std::sort(runs.begin(), runs.end(), [](const Run &a, const Run &b) { return a.dst < b.dst; });
-    // 1 KB chunks on 128-byte lines (the CRS values are 128-byte aligned: checked at launch): 16 entries per line
-    std::vector<int32_t> chunks;
-    for (const Run &r : runs) {
-      const int64_t dbeg = r.dst, dend = static_cast<int64_t>(r.dst) + r.len;
-      for (int64_t c = dbeg / 16 * 16; c < dend; c += 128) {
-        chunks.push_back(static_cast<int32_t>(c / 2));                    // destination / 16 bytes
-        chunks.push_back(static_cast<int32_t>(r.src + (c - dbeg)));       // source entry of lane 0's first double
-        chunks.push_back(static_cast<int32_t>(dbeg));
-        chunks.push_back(static_cast<int32_t>(dend));
-      }
-    }
+    const CopyPlan cp = build_copy_plan(block_pattern_copy_runs(h), d.nnz);
     bp.rep_seg.upload(rseg);
     bp.rep_wg_seg_ptr.upload(rptr);
-    bp.copy_chunks.upload(chunks);
-    bp.copy_runs = static_cast<int>(chunks.size() / 4);
+    bp.copy_items.upload(cp.item);
+    bp.copy_segs.upload(cp.seg);
+    bp.copy_num_items = cp.num_items();
+    bp.copy_num_segs = cp.num_segs();
     bp.dev_rep = d;
     bp.dev_rep.seg = bp.rep_seg.data();
     bp.dev_rep.wg_seg_ptr = bp.rep_wg_seg_ptr.data();
@@ -2439,7 +2427,9 @@ void AssemblyManager::launchRowOwner(bool compute_jacobian, bool overwrite, doub
     if (bpat_.usable && bpat_.db_mode && out.overwrite && !bpat_.dev.timing && (reinterpret_cast<uintptr_t>(out.vals) & 127u) == 0) {  // (the copy's chunks sit on 128-byte lines of the caller's array)
       // geometry-database mode: the representatives' rows, then their copies (same stream: ordered)
       launch_block_pattern_jacobian(bpat_.dev_rep, out, su, st, s);
-      launch_replicate_runs(bpat_.copy_chunks.data(), bpat_.copy_runs, out.vals, s);
+      // (lines that mix copied and representative entries are stored whole: the representatives' lanes store back the
+      // bits they read, which the kernel above wrote earlier on this stream; no other wavefront writes those lines)
+      launch_line_copy(bpat_.copy_items.data(), bpat_.copy_num_items, bpat_.copy_segs.data(), bpat_.copy_num_segs, h_rowptr_[nrows_], out.vals, s);
       last_db_mode_ = 1;
     } else if (bpat_.usable) {
       last_db_mode_ = 0;

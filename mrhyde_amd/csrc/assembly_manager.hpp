@@ -139,7 +139,7 @@ class AssemblyManager {
   bool porousDirectUsable();
   // database mode of the direct form (uniform mesh, constant coefficients: every element matrix is the same): rows of
   // the same CLASS -- same incident local dofs, same column slots -- are equal, so the element threads store the entries
-  // of a few representative rows per class only and replicate_runs_kernel fills the rest
+  // of a few representative rows per class only and line_copy_kernel fills the rest
   struct PorousDatabase {
     int state = -1;  // -1 not tried, 0 not usable (why), 1 built
     std::string why;
@@ -149,12 +149,14 @@ class AssemblyManager {
     double uniform_key[5] = {0, 0, 0, 0, 0};  // (Kinv_xx, _yy, _zz, mobility, alpha_u) the tables were made for
     bool uniform_valid = false;
     int num_listed = 0;
-    DeviceBuffer<int32_t> diag, chunks;  // finishing pass: diagonal positions of the COMPUTED face rows; copy chunks
-    int num_chunks = 0, num_classes = 0;
+    DeviceBuffer<int32_t> diag;        // finishing pass: diagonal positions of the COMPUTED face rows
+    DeviceBuffer<int32_t> copy_items, copy_segs;  // the copy plan of the replicated rows (copy_plan.hpp)
+    int num_items = 0, num_segs = 0, num_classes = 0;
     bool axis_aligned = false;  // the common element shape is an axis-aligned box
     int64_t computed_rows = 0;
   } porous_db_;
   bool porousDatabaseUsable();
+  void launchDatabaseCopy(double *crs_vals);
   bool has_incidence_ = false;
   int max_row_ = 0;
   void prepareRowGather(bool need_jacobian, bool dense = true);
@@ -242,8 +244,8 @@ class AssemblyManager {
     // geometry-database mode (one shape in the block): the kernel on one representative block per role + replication
     bool db_mode = false;
     BlockPatternDev dev_rep;  // dev with the segment tables of the representatives
-    DeviceBuffer<int32_t> rep_seg, rep_wg_seg_ptr, copy_chunks;  // [chunks][4]: see launch_replicate_runs
-    int copy_runs = 0;                                           // chunks
+    DeviceBuffer<int32_t> rep_seg, rep_wg_seg_ptr, copy_items, copy_segs;  // the copy plan: copy_plan.hpp
+    int copy_num_items = 0, copy_num_segs = 0;
   } bpat_;
   void prepareBlockPattern();
 

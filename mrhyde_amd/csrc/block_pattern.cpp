@@ -761,4 +761,18 @@ void block_patterns_host_apply(const BlockPatternPlan &pl, const double *factors
   }
 }
 
+std::vector<CopyRun> block_pattern_copy_runs(const BlockPatternPlan &pl) {
+  std::vector<CopyRun> runs;
+  for (int k = 0; k < pl.num_roles; ++k) {
+    const int32_t *ro = &pl.role[static_cast<size_t>(k) * kBpRoleInts];
+    const int64_t row_base = (static_cast<int64_t>(ro[R_ROWB_HI]) << 32) | static_cast<uint32_t>(ro[R_ROWB_LO]);
+    const int nruns = ro[R_NRUNS], nblocks = ro[R_NBLOCKS];
+    const int32_t *rl = &pl.runlen[static_cast<size_t>(pl.role_runlen_off[k])];
+    for (int j = 1; j < nblocks; ++j)
+      for (int r = 0; r < nruns; ++r)
+        runs.push_back({pl.rowbase[static_cast<size_t>(row_base + r)], pl.rowbase[static_cast<size_t>(row_base + static_cast<int64_t>(j) * nruns + r)], rl[r]});
+  }
+  return runs;
+}
+
 }  // namespace mha

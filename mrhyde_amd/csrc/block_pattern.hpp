@@ -38,6 +38,7 @@
 #include <string>
 #include <vector>
 
+#include "copy_plan.hpp"
 #include "row_blocks.hpp"
 
 namespace mha {
@@ -102,5 +103,9 @@ BlockPatternPlan build_block_patterns(const RowBlocks &rb, int n, int nsym, cons
 // vals[...] = the CRS values; every entry of an owned row is written exactly once.  factors: [E][ke].
 void block_patterns_host_apply(const BlockPatternPlan &plan, const double *factors, double scale_u, double scale_t,
                                bool overwrite, double *vals);
+
+// Geometry-database mode: with one geometry shape the rows of a block depend on its role only, so the kernel runs on
+// every role's first block and its runs of consecutive rows are copied to the same runs of the role's other blocks.
+std::vector<CopyRun> block_pattern_copy_runs(const BlockPatternPlan &plan);
 
 }  // namespace mha

@@ -74,6 +74,52 @@ mha::AssemblyManager &mgr(mha_context *ctx) {
   }
   return ctx->mgr;
 }
+
+// the block-pattern plan of a mesh as the test hooks see it (element slots by column search on the host)
+mha::BlockPatternPlan test_block_patterns(int dim, int num_rows, int num_elems, int nnodes, int n, int nsym,
+                                          const double *nodes, const int32_t *lids, const int32_t *rowptr,
+                                          const int32_t *colind, const uint8_t *fixed, const double *khat,
+                                          int chunk_elems, int num_cus, int max_patterns) {
+  MHA_REQUIRE(nodes && lids && rowptr && colind && khat, MHA_ERR_INVALID, "null argument");
+  MHA_REQUIRE(num_rows > 0 && num_elems > 0 && n > 0 && n <= 255 && nsym > 0, MHA_ERR_INVALID, "bad sizes");
+  // element-major slot map by column search (the device builds the same map in build_elem_slot_map_kernel)
+  int max_row = 0;
+  for (int r = 0; r < num_rows; ++r) max_row = std::max(max_row, rowptr[r + 1] - rowptr[r]);
+  const int sb = max_row <= 256 ? 1 : 2;
+  std::vector<uint8_t> slot(static_cast<size_t>(num_elems) * n * n * sb);
+  for (int e = 0; e < num_elems; ++e)
+    for (int si = 0; si < n; ++si) {
+      const int row = lids[static_cast<size_t>(e) * n + si];
+      const int32_t *lo = colind + rowptr[row], *hi = colind + rowptr[row + 1];
+      for (int sj = 0; sj < n; ++sj) {
+        const int32_t *it = std::lower_bound(lo, hi, lids[static_cast<size_t>(e) * n + sj]);
+        MHA_REQUIRE(it != hi && *it == lids[static_cast<size_t>(e) * n + sj], MHA_ERR_INVALID, "graph misses an element coupling");
+        const size_t idx = (static_cast<size_t>(e) * n + si) * n + sj;
+        if (sb == 1) slot[idx] = static_cast<uint8_t>(it - lo);
+        else reinterpret_cast<uint16_t *>(slot.data())[idx] = static_cast<uint16_t>(it - lo);
+      }
+    }
+  mha::RowBlockCaps caps = mha::default_caps(dim, n);
+  caps.chunk_elems = chunk_elems > 0 ? chunk_elems : 16;
+  caps.max_rows = 4096;
+  caps.max_elems = 255;
+  caps.max_pairs = 1 << 20;
+  caps.max_acc = 1 << 30;
+  const mha::RowBlocks rb = mha::build_row_blocks(dim, nnodes, num_elems, n, num_rows, nodes, lids, rowptr, caps, fixed, 1);
+  const mha::BlockPatternPlan pl = mha::build_block_patterns(rb, n, nsym, rowptr, fixed, slot.data(), sb, khat,
+                                                             num_cus > 0 ? num_cus : 8, size_t(150) * 1024,
+                                                             max_patterns > 0 ? max_patterns : 256);
+  MHA_REQUIRE(pl.usable, MHA_ERR_INVALID, "row blocks do not group: " << pl.why);
+  return pl;
+}
+
+void copy_plan_counts(const mha::CopyPlan &cp, int *counts) {
+  counts[0] = cp.num_items();
+  counts[1] = cp.num_segs() - mha::kCopySegRegs;  // (without the sentinels)
+  counts[2] = cp.max_item_segs;
+  counts[3] = mha::kCopySpanEntries;
+  counts[4] = mha::kCopySegRegs;
+}
 }  // namespace
 
 extern "C" {
@@ -637,47 +683,64 @@ int mha_scatter_plan_apply(const mha_scatter_plan *p, const double *blocks_dev, 
 
 void mha_scatter_plan_destroy(mha_scatter_plan *p) { delete p; }
 
+
 int mha_test_block_patterns_host_apply(int dim, int num_rows, int num_elems, int nnodes, int n, int nsym,
                                        const double *nodes, const int32_t *lids, const int32_t *rowptr,
                                        const int32_t *colind, const uint8_t *fixed, const double *khat,
                                        const double *factors, double scale_u, double scale_t, int chunk_elems,
                                        int num_cus, int max_patterns, double *vals, int *counts) {
   return guarded([&] {
-    MHA_REQUIRE(nodes && lids && rowptr && colind && khat && factors && vals && counts, MHA_ERR_INVALID, "null argument");
-    MHA_REQUIRE(num_rows > 0 && num_elems > 0 && n > 0 && n <= 255 && nsym > 0, MHA_ERR_INVALID, "bad sizes");
-    // element-major slot map by column search (the device builds the same map in build_elem_slot_map_kernel)
-    int max_row = 0;
-    for (int r = 0; r < num_rows; ++r) max_row = std::max(max_row, rowptr[r + 1] - rowptr[r]);
-    const int sb = max_row <= 256 ? 1 : 2;
-    std::vector<uint8_t> slot(static_cast<size_t>(num_elems) * n * n * sb);
-    for (int e = 0; e < num_elems; ++e)
-      for (int si = 0; si < n; ++si) {
-        const int row = lids[static_cast<size_t>(e) * n + si];
-        const int32_t *lo = colind + rowptr[row], *hi = colind + rowptr[row + 1];
-        for (int sj = 0; sj < n; ++sj) {
-          const int32_t *it = std::lower_bound(lo, hi, lids[static_cast<size_t>(e) * n + sj]);
-          MHA_REQUIRE(it != hi && *it == lids[static_cast<size_t>(e) * n + sj], MHA_ERR_INVALID, "graph misses an element coupling");
-          const size_t idx = (static_cast<size_t>(e) * n + si) * n + sj;
-          if (sb == 1) slot[idx] = static_cast<uint8_t>(it - lo);
-          else reinterpret_cast<uint16_t *>(slot.data())[idx] = static_cast<uint16_t>(it - lo);
-        }
-      }
-    mha::RowBlockCaps caps = mha::default_caps(dim, n);
-    caps.chunk_elems = chunk_elems > 0 ? chunk_elems : 16;
-    caps.max_rows = 4096;
-    caps.max_elems = 255;
-    caps.max_pairs = 1 << 20;
-    caps.max_acc = 1 << 30;
-    const mha::RowBlocks rb = mha::build_row_blocks(dim, nnodes, num_elems, n, num_rows, nodes, lids, rowptr, caps, fixed, 1);
-    const mha::BlockPatternPlan pl = mha::build_block_patterns(rb, n, nsym, rowptr, fixed, slot.data(), sb, khat,
-                                                               num_cus > 0 ? num_cus : 8, size_t(150) * 1024,
-                                                               max_patterns > 0 ? max_patterns : 256);
-    MHA_REQUIRE(pl.usable, MHA_ERR_INVALID, "row blocks do not group: " << pl.why);
+    MHA_REQUIRE(factors && vals && counts, MHA_ERR_INVALID, "null argument");
+    const mha::BlockPatternPlan pl = test_block_patterns(dim, num_rows, num_elems, nnodes, n, nsym, nodes, lids, rowptr,
+                                                         colind, fixed, khat, chunk_elems, num_cus, max_patterns);
     counts[0] = pl.num_patterns;
     counts[1] = pl.num_roles;
     counts[2] = pl.num_wgs;
     counts[3] = pl.num_parts;
     mha::block_patterns_host_apply(pl, factors, scale_u, scale_t, true, vals);
+  });
+}
+
+
+int mha_test_copy_plan_host_apply(int64_t nnz, int64_t num_runs, const int64_t *runs, double *vals, int32_t *stores,
+                                  int64_t stores_len, int *counts) {
+  return guarded([&] {
+    MHA_REQUIRE(vals && stores && counts && (runs || num_runs == 0), MHA_ERR_INVALID, "null argument");
+    std::vector<mha::CopyRun> rv(static_cast<size_t>(num_runs));
+    for (int64_t i = 0; i < num_runs; ++i) rv[i] = {runs[3 * i], runs[3 * i + 1], runs[3 * i + 2]};
+    const mha::CopyPlan cp = mha::build_copy_plan(std::move(rv), nnz);
+    MHA_REQUIRE(stores_len >= (nnz + mha::kCopySpanEntries - 1) / mha::kCopySpanEntries * mha::kCopySpanEntries,
+                MHA_ERR_INVALID, "store counters must cover whole spans");
+    copy_plan_counts(cp, counts);
+    mha::copy_plan_host_apply(cp, vals, stores);
+  });
+}
+
+int mha_test_block_pattern_copy_plan(int dim, int num_rows, int num_elems, int nnodes, int n, int nsym,
+                                     const double *nodes, const int32_t *lids, const int32_t *rowptr,
+                                     const int32_t *colind, const uint8_t *fixed, const double *khat,
+                                     const double *factors, int chunk_elems, int num_cus, int max_patterns,
+                                     double *vals_full, double *vals_db, int32_t *stores, int64_t stores_len,
+                                     int *counts) {
+  return guarded([&] {
+    MHA_REQUIRE(factors && vals_full && vals_db && stores && counts, MHA_ERR_INVALID, "null argument");
+    const mha::BlockPatternPlan pl = test_block_patterns(dim, num_rows, num_elems, nnodes, n, nsym, nodes, lids, rowptr,
+                                                         colind, fixed, khat, chunk_elems, num_cus, max_patterns);
+    const int64_t nnz = rowptr[num_rows];
+    mha::block_patterns_host_apply(pl, factors, 1.0, 1.0, true, vals_full);
+    const std::vector<mha::CopyRun> runs = mha::block_pattern_copy_runs(pl);
+    std::vector<uint8_t> copied(static_cast<size_t>(nnz), 0);
+    for (const mha::CopyRun &r : runs)
+      for (int64_t k = 0; k < r.len; ++k) copied[r.dst + k] = 1;
+    for (int64_t k = 0; k < nnz; ++k)  // the representatives' entries (and any no block owns): in place
+      if (!copied[k]) vals_db[k] = vals_full[k];
+    const mha::CopyPlan cp = mha::build_copy_plan(runs, nnz);
+    MHA_REQUIRE(stores_len >= (nnz + mha::kCopySpanEntries - 1) / mha::kCopySpanEntries * mha::kCopySpanEntries,
+                MHA_ERR_INVALID, "store counters must cover whole spans");
+    copy_plan_counts(cp, counts);
+    counts[5] = static_cast<int>(runs.size());
+    counts[6] = pl.num_roles;
+    mha::copy_plan_host_apply(cp, vals_db, stores);
   });
 }
 

@@ -21,6 +21,24 @@ int mha_test_block_patterns_host_apply(int dim, int num_rows, int num_elems, int
                                        const double *factors, double scale_u, double scale_t, int chunk_elems,
                                        int num_cus, int max_patterns, double *vals, int *counts);
 
+/* The database modes' line-aligned copy plan (csrc/copy_plan.hpp), built from runs [num_runs][3] = (source entry,
+ * destination entry, length) inside vals[0, nnz) and applied on the host with the copy kernel's lane logic
+ * (kernels/line_copy.hip).  stores [stores_len >= nnz rounded up to whole spans]: incremented per stored entry.
+ * counts[5] = {work items, segments, most segments of one item, entries per span, segment records held at once}. */
+int mha_test_copy_plan_host_apply(int64_t nnz, int64_t num_runs, const int64_t *runs, double *vals, int32_t *stores,
+                                  int64_t stores_len, int *counts);
+
+/* The geometry-database mode on the host: the block-pattern plan of the mesh (as mha_test_block_patterns_host_apply,
+ * scales 1), vals_full = every row block assembled; vals_db (caller-filled, e.g. NaN) gets the entries no copy run
+ * covers from vals_full (the representatives') and then the copy plan of block_pattern_copy_runs.
+ * counts[7] = the five of mha_test_copy_plan_host_apply, copy runs, roles. */
+int mha_test_block_pattern_copy_plan(int dim, int num_rows, int num_elems, int nnodes, int n, int nsym,
+                                     const double *nodes, const int32_t *lids, const int32_t *rowptr,
+                                     const int32_t *colind, const uint8_t *fixed, const double *khat,
+                                     const double *factors, int chunk_elems, int num_cus, int max_patterns,
+                                     double *vals_full, double *vals_db, int32_t *stores, int64_t stores_len,
+                                     int *counts);
+
 #ifdef __cplusplus
 }
 #endif
