@@ -370,9 +370,9 @@ void AssemblyManager::launchDatabaseCopy(double *crs_vals) {
 bool AssemblyManager::porousDirectUsable() {
   if (porous_direct_ >= 0) return porous_direct_ == 1;
   porous_direct_ = 0;
-  const char *m = std::getenv("MHA_POROUS_DIRECT"), *k = std::getenv("MHA_POROUS_KERNEL"), *g = std::getenv("MHA_GATHER_ORDER");
+  const char *m = std::getenv("MHA_POROUS_DIRECT"), *k = std::getenv("MHA_POROUS_KERNEL");
   if (m && m[0] == '0') { porous_direct_why_ = "MHA_POROUS_DIRECT=0"; return false; }
-  if ((k && k[0] == 'e') || (g && g[0] == 'p')) { porous_direct_why_ = "point engine / position order forced"; return false; }
+  if (k && k[0] == 'e') { porous_direct_why_ = "point engine forced"; return false; }
   if (!physics_ || physics_->label != "porousMixed" || n_ != 1 + 2 * dim_) { porous_direct_why_ = "not the lowest-order mixed element"; return false; }
   std::vector<int32_t> ptr, elem, lpos;
   build_row_incidence(nrows_, nelem_, n_, h_lids_.data(), ptr, elem, lpos);
@@ -655,35 +655,20 @@ void AssemblyManager::assembleJacRes(int flags, int path, const double *u, const
     path = MHA_PATH_ROW_GATHER;
   }
   if (path == MHA_PATH_AUTO) {
-    if (!ro_.ready && !ro_.failed && thermal_row_owner_supported(dim_, order_, ref_.nq1)) {
-      try {
-        prepareRowOwner();
-      } catch (const Error &) {  // e.g. a row exceeds the row-block caps: AUTO keeps the general path, once and for all
-        ro_ = RowOwnerData();
-        ro_.failed = true;
-      }
-    }
+    tryPrepareRowOwner();
     // affine elements with constant coefficients: the fused affine row-owner kernels; general elements / variable
     // coefficients: the general row-owner kernel; what neither covers: dense element matrices + the row gather
-    static const bool no_general = [] { const char *m = std::getenv("MHA_GENERAL"); return m && m[0] == 'g'; }();  // "gather"
     if (rowOwnerUsable(nullptr)) {
       path = MHA_PATH_ROW_OWNER;
     } else {
-      if (!no_general) prepareGeneralRowOwner();
-      path = (!no_general && gro_.usable) ? MHA_PATH_ROW_OWNER : MHA_PATH_ROW_GATHER;
+      prepareGeneralRowOwner();
+      path = gro_.usable ? MHA_PATH_ROW_OWNER : MHA_PATH_ROW_GATHER;
     }
   }
   int row_owner_kind = 0;  // 1: affine pair of kernels, 2: general-element kernel
   if (path == MHA_PATH_ROW_OWNER) {
     std::string why;
-    if (!ro_.ready && !ro_.failed && thermal_row_owner_supported(dim_, order_, ref_.nq1)) {
-      try {
-        prepareRowOwner();
-      } catch (const Error &) {
-        ro_ = RowOwnerData();
-        ro_.failed = true;
-      }
-    }
+    tryPrepareRowOwner();
     if (rowOwnerUsable(&why)) {
       row_owner_kind = 1;
     } else {
@@ -726,140 +711,9 @@ void AssemblyManager::assembleJacRes(int flags, int path, const double *u, const
       physics_->volumeResidual();
       break;
     }
-    case MHA_PATH_ROW_GATHER: {
-      // dense element matrices from the element kernel (stored, not accumulated), then one wavefront per CRS row
-      ElemOut o;
-      bool dof_order = false;
-      o.compute_jacobian = compute_jacobian ? 1 : 0;
-      o.local_store = 1;
-      o.local_J = compute_jacobian ? d_gather_J_.data() : nullptr;
-      o.local_res = d_gather_res_.data();
-      // thermal: the element matrices come from the specialised general-element kernel (kernels/thermal_general.hip;
-      // perturbed config 2: 4.1 ms against 7.7 ms with the point engine); MHA_ROW_GATHER_KERNEL=engine forces the engine
-      static const bool use_general = [] { const char *m = std::getenv("MHA_ROW_GATHER_KERNEL"); return !(m && m[0] == 'e'); }();
-      if (!engineOnly() && use_general && thermal_row_owner_supported(dim_, order_, ref_.nq1)) {
-        wkset_.first_elem = 0;
-        wkset_.numElem = nelem_;
-        wkset_.res = o;
-        useGeneralKernel(false);
-        if (!wkset_.use_general) {
-          // MHA_BASELINE_ELEMENT_KERNEL=1 (cross-check knob): the baseline kernel ACCUMULATES into local_J / local_res
-          // (updateJac / updateRes convention) and ignores local_store, so the scratch must start from zero
-          if (compute_jacobian) MHA_HIP(hipMemsetAsync(d_gather_J_.data(), 0, sizeof(double) * d_gather_J_.size(), stream_));
-          MHA_HIP(hipMemsetAsync(d_gather_res_.data(), 0, sizeof(double) * d_gather_res_.size(), stream_));
-        }
-        physics_->volumeResidual();
-      } else {
-        // porousMixed: its thread-per-element kernel writes the element arrays in dof order, straight from registers
-        // (kernels/porous_element.hip); MHA_GATHER_ORDER=pos keeps the LID-position order and the LDS staging
-        static const bool by_pos = [] {
-          const char *m = std::getenv("MHA_GATHER_ORDER"), *k = std::getenv("MHA_POROUS_KERNEL");
-          return (m && m[0] == 'p') || (k && k[0] == 'e');  // the point engine writes LID-position order only
-        }();
-        // (the same predicate launch_row_gather has for dof-ordered arrays -- short rows, one-byte slots: a porousMixed
-        // block with a wider caller graph or 16-bit slots keeps the position order instead of failing)
-        dof_order = !by_pos && !adjoint && !lump_mass && physics_->label == "porousMixed" && max_row_ <= 32 && n_ <= 16 &&
-                    elem_slot_bytes_ == 1;
-        if (porous_direct && elem_slot_bytes_ == 1) {
-          d_direct_part_.resize(static_cast<size_t>(nrows_) * 4);
-          o.local_J = nullptr;
-          o.local_res = nullptr;
-          o.direct_part = d_direct_part_.data();
-          o.direct_slot = static_cast<const uint8_t *>(d_elem_slot_.data());
-          o.direct_side = d_direct_side_.data();
-          o.direct_vals = compute_jacobian ? crs_vals : nullptr;
-          static const bool porous_nt = [] { const char *m = std::getenv("MHA_POROUS_NT"); return m && m[0] == '1'; }();  // experiment: nontemporal entry stores
-          o.direct_overwrite = overwrite ? (porous_nt ? 2 : 1) : 0;
-          // database mode: overwriting assemblies of a uniform block with constant permeability / mobility
-          bool pdb = overwrite && compute_jacobian && (reinterpret_cast<uintptr_t>(crs_vals) & 127u) == 0;
-          for (const char *name : {"Kinv_xx", "Kinv_yy", "Kinv_zz", "total_mobility"})
-            pdb = pdb && functions_.has(name) && functions_.evaluate(name).kind == MHA_FUNC_CONSTANT;
-          pdb = pdb && porousDatabaseUsable();
-          static const bool two_kernels = [] { const char *m = std::getenv("MHA_POROUS_DB_LEAN"); return !(m && m[0] == '0'); }();
-          if (pdb && two_kernels && functions_.evaluate("source").kind != MHA_FUNC_EXPRESSION) {
-            // database mode: the lean build (residual parts only) over all elements, then the full build over the few
-            // elements incident to computed rows (same records, rewritten with the diagonal parts; their entries)
-            o.direct_axis_aligned = porous_db_.axis_aligned ? 1 : 0;
-            ElemOut lean = o;
-            lean.direct_res_only = 1;
-            static const bool matvec = [] { const char *m = std::getenv("MHA_POROUS_DB_MATVEC"); return !(m && m[0] == '0'); }();
-            if (matvec) {
-              // the residual of a linear module from the element matrix: the dense kernel on element 0 leaves the matrix
-              // of the uniform block (dof order) in front of the point tables (kernels/porous_element.hip)
-              // (made again only when a coefficient or the time-integration factor has changed)
-              const double key[5] = {functions_.evaluate("Kinv_xx").amp, functions_.evaluate("Kinv_yy").amp,
-                                     functions_.evaluate("Kinv_zz").amp, functions_.evaluate("total_mobility").amp, wkset_.time_dev.alpha_u};
-              if (!porous_db_.uniform_valid || std::memcmp(key, porous_db_.uniform_key, sizeof(key)) != 0) {
-                porous_db_.uniform.resize(static_cast<size_t>(n_) * n_ + static_cast<size_t>(nq_) * (dim_ + 1) + n_);
-                ElemOut dense;
-                dense.compute_jacobian = 1;
-                dense.local_store = 1;
-                dense.local_dof_order = 1;
-                dense.local_J = porous_db_.uniform.data();
-                dense.local_res = porous_db_.uniform.data() + static_cast<size_t>(n_) * n_ + static_cast<size_t>(nq_) * (dim_ + 1);
-                launchPointEngine(1, dense, 0, 1);
-                launch_porous_uniform_points(blockDev(), porous_db_.uniform.data(), stream_);
-                std::memcpy(porous_db_.uniform_key, key, sizeof(key));
-                porous_db_.uniform_valid = true;
-              }
-              lean.direct_uniform = porous_db_.uniform.data();
-            }
-            o.direct_elist = porous_db_.elist.data();
-            if (lean.direct_uniform) {
-              // the two kernels write the records of disjoint sets of elements: side by side on two streams
-              lean.direct_jacflag = porous_db_.jacflag.data();
-              if (!side_stream_) {
-                MHA_HIP(hipStreamCreateWithFlags(&side_stream_, hipStreamNonBlocking));
-                MHA_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-                MHA_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-              }
-              MHA_HIP(hipEventRecord(ev_fork_, stream_));
-              MHA_HIP(hipStreamWaitEvent(side_stream_, ev_fork_, 0));
-              wkset_.stream = side_stream_;
-              launchPointEngine(compute_jacobian, o, 0, porous_db_.num_listed);
-              wkset_.stream = stream_;
-              MHA_HIP(hipEventRecord(ev_join_, side_stream_));
-              launchPointEngine(compute_jacobian, lean, 0, nelem_);
-              MHA_HIP(hipStreamWaitEvent(stream_, ev_join_, 0));
-            } else {
-              launchPointEngine(compute_jacobian, lean, 0, nelem_);
-              launchPointEngine(compute_jacobian, o, 0, porous_db_.num_listed);
-            }
-            launch_porous_direct_finish(blockDev(), d_inc_ptr_.data(), porous_db_.diag.data(), o.direct_part, res, o.direct_vals, 1, stream_);
-            // (lines that mix copied and computed entries are stored whole: those lanes store back the bits they read,
-            // written earlier on this stream -- the side stream's element kernel joined above; no other wavefront
-            // writes those lines)
-            launchDatabaseCopy(crs_vals);
-            last_porous_direct_ = 2;
-            break;
-          }
-          if (pdb) o.direct_jacflag = porous_db_.jacflag.data();
-          if (!compute_jacobian) o.direct_res_only = 1;  // residual-only assemblies: the lean build
-          launchPointEngine(compute_jacobian, o, 0, nelem_);
-          launch_porous_direct_finish(blockDev(), d_inc_ptr_.data(), pdb ? porous_db_.diag.data() : d_direct_diag_.data(), o.direct_part,
-                                      res, o.direct_vals, overwrite ? 1 : 0, stream_);
-          if (pdb) launchDatabaseCopy(crs_vals);  // (in-place lanes: as above, every writer ran earlier on stream_)
-          last_porous_direct_ = pdb ? 2 : 1;
-          break;
-        }
-        last_porous_direct_ = 0;
-        o.local_dof_order = dof_order ? 1 : 0;
-        launchPointEngine(compute_jacobian, o, 0, nelem_);
-      }
-      RowGatherDev g;
-      g.inc_dof = dof_order ? d_inc_dof_.data() : nullptr;
-      g.inc_ptr = d_inc_ptr_.data();
-      g.inc_elem = d_inc_elem_.data();
-      g.inc_pos = d_inc_pos_.data();
-      g.slot = d_elem_slot_.data();
-      g.slot_bytes = elem_slot_bytes_;
-      g.max_row = max_row_;
-      g.adjoint = adjoint ? 1 : 0;
-      g.lump_mass = lump_mass ? 1 : 0;
-      launch_row_gather(blockDev(), g, o.local_J, o.local_res, res, compute_jacobian ? crs_vals : nullptr,
-                        overwrite ? 1 : 0, stream_);
+    case MHA_PATH_ROW_GATHER:
+      assembleRowGather(compute_jacobian, overwrite, adjoint, lump_mass, porous_direct, res, crs_vals);
       break;
-    }
     case MHA_PATH_POINT_ENGINE: {
       ElemOut o;
       o.compute_jacobian = compute_jacobian ? 1 : 0;
@@ -902,6 +756,142 @@ void AssemblyManager::assembleJacRes(int flags, int path, const double *u, const
   timedEnd();
   last_path_ = path;
   last_row_owner_kind_ = row_owner_kind;
+}
+
+// Builds the affine row-owner partition once per mesh / graph.  A failure (e.g. a row exceeds the row-block caps) is
+// remembered: AUTO keeps the general path, once and for all.
+void AssemblyManager::tryPrepareRowOwner() {
+  if (ro_.ready || ro_.failed || !thermal_row_owner_supported(dim_, order_, ref_.nq1)) return;
+  try {
+    prepareRowOwner();
+  } catch (const Error &) {
+    ro_ = RowOwnerData();
+    ro_.failed = true;
+  }
+}
+
+// Dense element matrices from the element kernel (stored, not accumulated), then one wavefront per CRS row.
+void AssemblyManager::assembleRowGather(int compute_jacobian, bool overwrite, bool adjoint, bool lump_mass,
+                                        bool porous_direct, double *res, double *crs_vals) {
+  ElemOut o;
+  bool dof_order = false;
+  o.compute_jacobian = compute_jacobian ? 1 : 0;
+  o.local_store = 1;
+  o.local_J = compute_jacobian ? d_gather_J_.data() : nullptr;
+  o.local_res = d_gather_res_.data();
+  // thermal: the element matrices come from the specialised general-element kernel (kernels/thermal_general.hip;
+  // perturbed config 2: 4.1 ms against 7.7 ms with the point engine); MHA_ROW_GATHER_KERNEL=engine forces the engine
+  static const bool use_general = [] { const char *m = std::getenv("MHA_ROW_GATHER_KERNEL"); return !(m && m[0] == 'e'); }();
+  if (!engineOnly() && use_general && thermal_row_owner_supported(dim_, order_, ref_.nq1)) {
+    wkset_.first_elem = 0;
+    wkset_.numElem = nelem_;
+    wkset_.res = o;
+    useGeneralKernel(false);
+    if (!wkset_.use_general) {
+      // MHA_BASELINE_ELEMENT_KERNEL=1 (cross-check knob): the baseline kernel ACCUMULATES into local_J / local_res
+      // (updateJac / updateRes convention) and ignores local_store, so the scratch must start from zero
+      if (compute_jacobian) MHA_HIP(hipMemsetAsync(d_gather_J_.data(), 0, sizeof(double) * d_gather_J_.size(), stream_));
+      MHA_HIP(hipMemsetAsync(d_gather_res_.data(), 0, sizeof(double) * d_gather_res_.size(), stream_));
+    }
+    physics_->volumeResidual();
+  } else {
+    // porousMixed: its thread-per-element kernel writes the element arrays in dof order, straight from registers
+    // (kernels/porous_element.hip); the point engine (MHA_POROUS_KERNEL=engine) writes LID-position order only
+    static const bool by_pos = [] { const char *k = std::getenv("MHA_POROUS_KERNEL"); return k && k[0] == 'e'; }();
+    // (the same predicate launch_row_gather has for dof-ordered arrays -- short rows, one-byte slots: a porousMixed
+    // block with a wider caller graph or 16-bit slots keeps the position order instead of failing)
+    dof_order = !by_pos && !adjoint && !lump_mass && physics_->label == "porousMixed" && max_row_ <= 32 && n_ <= 16 &&
+                elem_slot_bytes_ == 1;
+    if (porous_direct && elem_slot_bytes_ == 1) {
+      assemblePorousDirect(o, compute_jacobian, overwrite, res, crs_vals);
+      return;
+    }
+    last_porous_direct_ = 0;
+    o.local_dof_order = dof_order ? 1 : 0;
+    launchPointEngine(compute_jacobian, o, 0, nelem_);
+  }
+  RowGatherDev g;
+  g.inc_dof = dof_order ? d_inc_dof_.data() : nullptr;
+  g.inc_ptr = d_inc_ptr_.data();
+  g.inc_elem = d_inc_elem_.data();
+  g.inc_pos = d_inc_pos_.data();
+  g.slot = d_elem_slot_.data();
+  g.slot_bytes = elem_slot_bytes_;
+  g.max_row = max_row_;
+  g.adjoint = adjoint ? 1 : 0;
+  g.lump_mass = lump_mass ? 1 : 0;
+  launch_row_gather(blockDev(), g, o.local_J, o.local_res, res, compute_jacobian ? crs_vals : nullptr,
+                    overwrite ? 1 : 0, stream_);
+}
+
+// porousMixed, direct form: the element threads store into the CRS, a finishing pass sums residual and diagonal parts.
+// o: the row-gather outputs, redirected here.
+void AssemblyManager::assemblePorousDirect(ElemOut o, int compute_jacobian, bool overwrite, double *res, double *crs_vals) {
+  d_direct_part_.resize(static_cast<size_t>(nrows_) * 4);
+  o.local_J = nullptr;
+  o.local_res = nullptr;
+  o.direct_part = d_direct_part_.data();
+  o.direct_slot = static_cast<const uint8_t *>(d_elem_slot_.data());
+  o.direct_side = d_direct_side_.data();
+  o.direct_vals = compute_jacobian ? crs_vals : nullptr;
+  o.direct_overwrite = overwrite ? 1 : 0;
+  // database mode: overwriting assemblies of a uniform block with constant permeability / mobility
+  bool pdb = overwrite && compute_jacobian && (reinterpret_cast<uintptr_t>(crs_vals) & 127u) == 0;
+  for (const char *name : {"Kinv_xx", "Kinv_yy", "Kinv_zz", "total_mobility"})
+    pdb = pdb && functions_.has(name) && functions_.evaluate(name).kind == MHA_FUNC_CONSTANT;
+  pdb = pdb && porousDatabaseUsable();
+  if (pdb && functions_.evaluate("source").kind != MHA_FUNC_EXPRESSION) {
+    // database mode: the lean build (residual parts only) over all elements, then the full build over the few
+    // elements incident to computed rows (same records, rewritten with the diagonal parts; their entries)
+    o.direct_axis_aligned = porous_db_.axis_aligned ? 1 : 0;
+    ElemOut lean = o;
+    lean.direct_res_only = 1;
+    // the residual of a linear module from the element matrix: the dense kernel on element 0 leaves the matrix
+    // of the uniform block (dof order) in front of the point tables (kernels/porous_element.hip)
+    // (made again only when a coefficient or the time-integration factor has changed)
+    const double key[5] = {functions_.evaluate("Kinv_xx").amp, functions_.evaluate("Kinv_yy").amp,
+                           functions_.evaluate("Kinv_zz").amp, functions_.evaluate("total_mobility").amp, wkset_.time_dev.alpha_u};
+    if (!porous_db_.uniform_valid || std::memcmp(key, porous_db_.uniform_key, sizeof(key)) != 0) {
+      porous_db_.uniform.resize(static_cast<size_t>(n_) * n_ + static_cast<size_t>(nq_) * (dim_ + 1) + n_);
+      ElemOut dense;
+      dense.compute_jacobian = 1;
+      dense.local_store = 1;
+      dense.local_dof_order = 1;
+      dense.local_J = porous_db_.uniform.data();
+      dense.local_res = porous_db_.uniform.data() + static_cast<size_t>(n_) * n_ + static_cast<size_t>(nq_) * (dim_ + 1);
+      launchPointEngine(1, dense, 0, 1);
+      launch_porous_uniform_points(blockDev(), porous_db_.uniform.data(), stream_);
+      std::memcpy(porous_db_.uniform_key, key, sizeof(key));
+      porous_db_.uniform_valid = true;
+    }
+    lean.direct_uniform = porous_db_.uniform.data();
+    o.direct_elist = porous_db_.elist.data();
+    // the two kernels write the records of disjoint sets of elements: side by side on two streams
+    lean.direct_jacflag = porous_db_.jacflag.data();
+    ensureSideStream();
+    MHA_HIP(hipEventRecord(ev_fork_, stream_));
+    MHA_HIP(hipStreamWaitEvent(side_stream_, ev_fork_, 0));
+    wkset_.stream = side_stream_;
+    launchPointEngine(compute_jacobian, o, 0, porous_db_.num_listed);
+    wkset_.stream = stream_;
+    MHA_HIP(hipEventRecord(ev_join_, side_stream_));
+    launchPointEngine(compute_jacobian, lean, 0, nelem_);
+    MHA_HIP(hipStreamWaitEvent(stream_, ev_join_, 0));
+    launch_porous_direct_finish(blockDev(), d_inc_ptr_.data(), porous_db_.diag.data(), o.direct_part, res, o.direct_vals, 1, stream_);
+    // (lines that mix copied and computed entries are stored whole: those lanes store back the bits they read,
+    // written earlier on this stream -- the side stream's element kernel joined above; no other wavefront
+    // writes those lines)
+    launchDatabaseCopy(crs_vals);
+    last_porous_direct_ = 2;
+    return;
+  }
+  if (pdb) o.direct_jacflag = porous_db_.jacflag.data();
+  if (!compute_jacobian) o.direct_res_only = 1;  // residual-only assemblies: the lean build
+  launchPointEngine(compute_jacobian, o, 0, nelem_);
+  launch_porous_direct_finish(blockDev(), d_inc_ptr_.data(), pdb ? porous_db_.diag.data() : d_direct_diag_.data(), o.direct_part,
+                              res, o.direct_vals, overwrite ? 1 : 0, stream_);
+  if (pdb) launchDatabaseCopy(crs_vals);  // (in-place lanes: as above, every writer ran earlier on stream_)
+  last_porous_direct_ = pdb ? 2 : 1;
 }
 
 // reference: updateJac / updateRes on the whole block (assemblyManager.cpp:7412-7455, 7115-7152)
@@ -1811,9 +1801,6 @@ void AssemblyManager::prepareRowOwner() {
     const long budget = 40 * 1024 - fixed_bytes;
     MHA_REQUIRE(budget >= 8 * 2 * max_row, MHA_ERR_INVALID, "row-owner kernel does not fit the LDS budget for this element");
     caps.max_acc = std::min(65534, static_cast<int>(budget / 8) / 2 * 2);
-    // tuning knobs (experiments): elements per Morton chunk and the accumulator cap
-    if (const char *e = std::getenv("MHA_RB_CHUNK")) caps.chunk_elems = std::max(1, std::atoi(e));
-    if (const char *e = std::getenv("MHA_RB_MAXACC")) caps.max_acc = std::max(2 * max_row, std::atoi(e));
   }
   ro.rb = build_row_blocks(dim_, nnodes_, nelem_, n_, nrows_, nodes.data(), h_lids_.data(), h_rowptr_.data(), caps,
                            has_fixed_ ? h_fixed_.data() : nullptr, ro.slot_bytes);
@@ -2063,13 +2050,10 @@ void AssemblyManager::prepareRowOwner() {
         if (it.second) shapes.insert(shapes.end(), rec, rec + 16);
         sidx[e] = it.first->second;
       }
-      const char *db = std::getenv("MHA_K1_DATABASE");
-      if (!(db && db[0] == '0')) {
-        ro.k1_shape.upload(shapes);
-        ro.k1_shape_idx.upload(sidx);
-        ro.k1_plan.shape = ro.k1_shape.data();
-        ro.k1_plan.shape_idx = ro.k1_shape_idx.data();
-      }
+      ro.k1_shape.upload(shapes);
+      ro.k1_shape_idx.upload(sidx);
+      ro.k1_plan.shape = ro.k1_shape.data();
+      ro.k1_plan.shape_idx = ro.k1_shape_idx.data();
       ro.k1_plan.num_shapes = static_cast<int>(seen.size());
       ro.num_shapes = ro.k1_plan.num_shapes;
     }
@@ -2092,7 +2076,6 @@ void AssemblyManager::prepareBlockPattern() {
   // no LDS accumulator to fit
   RowBlockCaps caps = default_caps(dim_, n_);
   caps.chunk_elems = 16;
-  if (const char *e = std::getenv("MHA_BP_CHUNK")) caps.chunk_elems = std::max(1, std::atoi(e));
   caps.max_rows = 4096;
   caps.max_elems = 255;
   caps.max_pairs = 1 << 20;
@@ -2115,15 +2098,13 @@ void AssemblyManager::prepareBlockPattern() {
   const int nsym = dim_ * (dim_ + 1) / 2;
   std::vector<double> khat(static_cast<size_t>(nsym + 1) * n_ * n_);
   ro_.khat.download(khat.data());
-  int num_cu = current_device_num_cus();
-  if (const char *m = std::getenv("MHA_BP_WGS")) num_cu = std::max(1, std::atoi(m));
   const BlockPatternPlan h = build_block_patterns(rb, n_, nsym, h_rowptr_.data(), has_fixed_ ? h_fixed_.data() : nullptr,
-                                                  slot.data(), elem_slot_bytes_, khat.data(), num_cu, size_t(142) * 1024, 256,
-                                                  std::getenv("MHA_BP_SEGBLOCKS") ? std::atoi(std::getenv("MHA_BP_SEGBLOCKS")) : 0);
+                                                  slot.data(), elem_slot_bytes_, khat.data(), current_device_num_cus(),
+                                                  size_t(142) * 1024, 256);
   bp.why = h.why;
   if (std::getenv("MHA_VERBOSE"))
-    fprintf(stderr, "[mrhyde_amd] block patterns: usable %d (%s), %d patterns, %d roles (%d with an LDS image), %d parts, %d workgroups, %lld MFMAs per assembly\n",
-            int(h.usable), h.why.c_str(), h.num_patterns, h.num_roles, h.num_image_roles, h.num_parts, h.num_wgs, (long long)h.mfma_per_assembly);
+    fprintf(stderr, "[mrhyde_amd] block patterns: usable %d (%s), %d patterns, %d roles, %d parts, %d workgroups, %lld MFMAs per assembly\n",
+            int(h.usable), h.why.c_str(), h.num_patterns, h.num_roles, h.num_parts, h.num_wgs, (long long)h.mfma_per_assembly);
   if (std::getenv("MHA_VERBOSE") && h.usable) {  // shapes of the units: (k-steps, tiles, tail, trim class) -> count
     std::map<std::vector<int>, int> shapes;
     for (int p = 0; p < h.num_parts; ++p) {
@@ -2142,42 +2123,29 @@ void AssemblyManager::prepareBlockPattern() {
   bp.role.upload(h.role);
   bp.seg.upload(h.seg);
   bp.wg_seg_ptr.upload(h.wg_seg_ptr);
-  bp.wg_seg_ptr_img.upload(h.wg_seg_ptr_img);
   bp.part_ptr.upload(h.part_ptr);
   bp.part_hdr.upload(h.part_hdr);
   bp.part_lane.upload(h.part_lane);
   bp.rowbase.upload(h.rowbase);
-  {
-    std::vector<int32_t> ct = h.chunk_tab;
-    if (ct.empty()) ct.assign(kBpChunkInts, 0);
-    bp.chunk_tab.upload(ct);
-  }
   bp.erec_elem.upload(h.erec_elem);
   bp.w.upload(h.w);
   bp.erec2.resize(h.erec_elem.size() * kBpRecDoubles);
   launch_build_erec2(static_cast<int64_t>(h.erec_elem.size()), nsym, bp.erec_elem.data(), ro_.geo.data(), bp.erec2.data(), stream_);
-  if (std::getenv("MHA_BP_TIMING")) bp.timing.resize(static_cast<size_t>(h.num_wgs) * kBpWaves * 8);
   BlockPatternDev &d = bp.dev;
   d.num_wgs = h.num_wgs;
   d.max_w_doubles = h.max_w_doubles;
   d.max_rec_doubles = h.max_rec_doubles;
-  d.dbg = 0;
-  if (const char *m = std::getenv("MHA_BP_DBG")) d.dbg = std::atoi(m);
   d.erec2 = bp.erec2.data();
   d.rowbase = bp.rowbase.data();
   d.w = bp.w.data();
   d.role = bp.role.data();
   d.seg = bp.seg.data();
   d.wg_seg_ptr = bp.wg_seg_ptr.data();
-  d.wg_seg_ptr_img = bp.wg_seg_ptr_img.data();
   d.has_direct = h.wg_seg_ptr.back() > h.wg_seg_ptr.front();
-  d.has_image = h.wg_seg_ptr_img.back() > h.wg_seg_ptr_img.front();
   d.part_ptr = bp.part_ptr.data();
   d.part_hdr = bp.part_hdr.data();
   d.part_lane = bp.part_lane.data();
-  d.chunk_tab = bp.chunk_tab.data();
   d.nnz = h_rowptr_[nrows_];
-  d.timing = bp.timing.empty() ? nullptr : bp.timing.data();
   MHA_HIP(hipStreamSynchronize(stream_));
   bp.usable = true;
   // Geometry-database mode (reference: identifyVolumetricDatabase, assemblyManager.cpp:4314-4467,
@@ -2186,7 +2154,7 @@ void AssemblyManager::prepareBlockPattern() {
   // replicated.  MHA_BP_DATABASE=0 keeps the full kernel.
   bp.db_mode = false;
   const char *dbm = std::getenv("MHA_BP_DATABASE");
-  if (ro_.num_shapes == 1 && !d.has_image && !(dbm && dbm[0] == '0')) {
+  if (ro_.num_shapes == 1 && !(dbm && dbm[0] == '0')) {
     std::vector<int32_t> rseg(static_cast<size_t>(h.num_roles) * 4, 0), rptr(static_cast<size_t>(h.num_roles) + 1, 0);
     for (int k = 0; k < h.num_roles; ++k) {
       rseg[4 * k] = k;
@@ -2205,7 +2173,6 @@ void AssemblyManager::prepareBlockPattern() {
     bp.dev_rep.seg = bp.rep_seg.data();
     bp.dev_rep.wg_seg_ptr = bp.rep_wg_seg_ptr.data();
     bp.dev_rep.num_wgs = h.num_roles;
-    bp.dev_rep.timing = nullptr;
     bp.db_mode = true;
   }
 }
@@ -2265,8 +2232,6 @@ void AssemblyManager::prepareGeneralRowOwner() {
   caps.max_rows = 128;
   caps.max_pairs = 256;
   caps.max_acc = 4352;
-  if (const char *e = std::getenv("MHA_GRO_CHUNK")) caps.chunk_elems = std::max(1, std::atoi(e));
-  if (const char *e = std::getenv("MHA_GRO_MAXACC")) caps.max_acc = std::max(2 * max_row, std::atoi(e));
   std::vector<double> nodes(static_cast<size_t>(nelem_) * nnodes_ * dim_);
   d_nodes_.download(nodes.data());
   try {
@@ -2330,20 +2295,8 @@ void AssemblyManager::launchGeneralRowOwner(bool compute_jacobian, bool overwrit
   out.compute_jacobian = compute_jacobian ? 1 : 0;
   out.ordered = ordered ? 1 : 0;
   MHA_REQUIRE(!ordered || !compute_jacobian, MHA_ERR_INVALID, "the ordered residual sums exist in the residual-only pass");
-  static const int wgs = [] { const char *m = std::getenv("MHA_GRO_WGS"); return m ? std::atoi(m) : 0; }();
-  const int nwg = wgs > 0 ? wgs : current_device_num_cus();
-  // profiling aid (env MHA_GRO_TIMING=<file>): cycles every wavefront spent in each phase of the last launch
-  static const char *timing_file = std::getenv("MHA_GRO_TIMING");
-  if (timing_file && gro_.timing.size() != static_cast<size_t>(nwg) * 8 * 8) gro_.timing.resize(static_cast<size_t>(nwg) * 8 * 8);
   launch_thermal_general_row_owner(dim_, order_, ref_.nq1, blockDev(), ph, generalRowBlocksDev(), gro_.slot.data(),
-                                   gro_.blk_rows.data(), d_gp1d_.data(), gro_.blk_hdr.data(),
-                                   timing_file ? gro_.timing.data() : nullptr, out, nwg, stream_);
-  if (timing_file) {
-    MHA_HIP(hipStreamSynchronize(stream_));
-    std::vector<long long> t(gro_.timing.size());
-    gro_.timing.download(t.data());
-    if (FILE *f = fopen(timing_file, "wb")) { fwrite(t.data(), sizeof(long long), t.size(), f); fclose(f); }
-  }
+                                   gro_.blk_rows.data(), d_gp1d_.data(), gro_.blk_hdr.data(), out, current_device_num_cus(), stream_);
 }
 
 RowBlocksDev AssemblyManager::rowBlocksDev() const {
@@ -2409,59 +2362,48 @@ void AssemblyManager::launchRowOwner(bool compute_jacobian, bool overwrite, doub
     if (compute_jacobian) launch_block_pattern_jacobian(bpat_.dev, out, ph.time.alpha_u * ph.diff.amp, ph.time.alpha_t * ph.rho.amp * ph.cp.amp, stream_);
     return;
   }
-  // K1 accumulates the residual with atomics: the fused zeroing becomes a (small) memset -- on the stream K1 runs on (with
-  // the side stream below it no longer sits in front of the Jacobian kernels)
-  static const int overlap_early = [] { const char *m = std::getenv("MHA_K1K2_OVERLAP"); return m ? std::atoi(m) : 1; }();
-  const bool memset_on_side = overwrite && overlap_early && compute_jacobian;
-  if (overwrite && !memset_on_side) MHA_HIP(hipMemsetAsync(res, 0, sizeof(double) * nrows_, stream_));
-  // K1 (residual, VALU-bound) and K2 (Jacobian, latency-bound) write different arrays: K2 goes first on the
-  // context's stream and K1 on a side stream, so that K1's workgroups fill the wave slots K2 leaves free
-  // (0.743 -> 0.686 ms per assembly on config 2, profiles/r1_ab_k1k2_overlap.log); MHA_K1K2_OVERLAP=0 serialises them
-  static const int overlap = [] { const char *m = std::getenv("MHA_K1K2_OVERLAP"); return m ? std::atoi(m) : 1; }();
   const double su = ph.time.alpha_u * ph.diff.amp, st = ph.time.alpha_t * ph.rho.amp * ph.cp.amp;
   auto residual = [&](hipStream_t s) {  // K1: one thread per element (default) or the 32-lanes-per-element form (MHA_K1=lanes)
     if (ro_.k1_thread) launch_thermal_affine_residual(dim_, order_, blockDev(), ph, ro_.geo.data(), ro_.tab1d, &ro_.k1_plan, res, ro_.max_abs_coord, s);
     else launch_thermal_affine_element(dim_, order_, ref_.nq1, blockDev(), ph, af, res, s);
   };
-  auto jacobian = [&](hipStream_t s) {  // K2: pattern GEMMs on the matrix cores when the rows group, row blocks otherwise
-    if (bpat_.usable && bpat_.db_mode && out.overwrite && !bpat_.dev.timing && (reinterpret_cast<uintptr_t>(out.vals) & 127u) == 0) {  // (the copy's chunks sit on 128-byte lines of the caller's array)
-      // geometry-database mode: the representatives' rows, then their copies (same stream: ordered)
-      launch_block_pattern_jacobian(bpat_.dev_rep, out, su, st, s);
-      // (lines that mix copied and representative entries are stored whole: the representatives' lanes store back the
-      // bits they read, which the kernel above wrote earlier on this stream; no other wavefront writes those lines)
-      launch_line_copy(bpat_.copy_items.data(), bpat_.copy_num_items, bpat_.copy_segs.data(), bpat_.copy_num_segs, h_rowptr_[nrows_], out.vals, s);
-      last_db_mode_ = 1;
-    } else if (bpat_.usable) {
-      last_db_mode_ = 0;
-      launch_block_pattern_jacobian(bpat_.dev, out, su, st, s);
-      if (bpat_.dev.timing) {  // profiling aid: wall-clock stamps of every wavefront of the last launch -> $MHA_BP_TIMING
-        MHA_HIP(hipStreamSynchronize(s));
-        std::vector<long long> t(bpat_.timing.size());
-        bpat_.timing.download(t.data());
-        if (FILE *f = fopen(std::getenv("MHA_BP_TIMING"), "wb")) { fwrite(t.data(), sizeof(long long), t.size(), f); fclose(f); }
-      }
-    } else {
-      launch_row_owner_jacobian(dim_, n_, rb, af, out, su, st, s);
-    }
-  };
-  if (overlap && compute_jacobian) {
-    if (!side_stream_) {
-      MHA_HIP(hipStreamCreateWithFlags(&side_stream_, hipStreamNonBlocking));
-      MHA_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
-      MHA_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-    }
-    MHA_HIP(hipEventRecord(ev_fork_, stream_));
-    MHA_HIP(hipStreamWaitEvent(side_stream_, ev_fork_, 0));
-    if (memset_on_side) MHA_HIP(hipMemsetAsync(res, 0, sizeof(double) * nrows_, side_stream_));
-    if (overlap == 2) residual(side_stream_);
-    jacobian(stream_);
-    if (overlap != 2) residual(side_stream_);
-    MHA_HIP(hipEventRecord(ev_join_, side_stream_));
-    MHA_HIP(hipStreamWaitEvent(stream_, ev_join_, 0));
+  // K1 accumulates the residual with atomics: the fused zeroing becomes a (small) memset on the stream K1 runs on
+  if (!compute_jacobian) {
+    if (overwrite) MHA_HIP(hipMemsetAsync(res, 0, sizeof(double) * nrows_, stream_));
+    residual(stream_);
     return;
   }
-  residual(stream_);
-  if (compute_jacobian) jacobian(stream_);
+  // K1 (residual, VALU-bound) and K2 (Jacobian, latency-bound) write different arrays: K2 goes first on the
+  // context's stream and K1 on a side stream, so that K1's workgroups fill the wave slots K2 leaves free
+  // (0.743 -> 0.686 ms per assembly on config 2, profiles/r1_ab_k1k2_overlap.log)
+  ensureSideStream();
+  MHA_HIP(hipEventRecord(ev_fork_, stream_));
+  MHA_HIP(hipStreamWaitEvent(side_stream_, ev_fork_, 0));
+  if (overwrite) MHA_HIP(hipMemsetAsync(res, 0, sizeof(double) * nrows_, side_stream_));
+  // K2: pattern GEMMs on the matrix cores when the rows group, row blocks otherwise
+  if (bpat_.usable && bpat_.db_mode && out.overwrite && (reinterpret_cast<uintptr_t>(out.vals) & 127u) == 0) {  // (the copy's chunks sit on 128-byte lines of the caller's array)
+    // geometry-database mode: the representatives' rows, then their copies (same stream: ordered)
+    launch_block_pattern_jacobian(bpat_.dev_rep, out, su, st, stream_);
+    // (lines that mix copied and representative entries are stored whole: the representatives' lanes store back the
+    // bits they read, which the kernel above wrote earlier on this stream; no other wavefront writes those lines)
+    launch_line_copy(bpat_.copy_items.data(), bpat_.copy_num_items, bpat_.copy_segs.data(), bpat_.copy_num_segs, h_rowptr_[nrows_], out.vals, stream_);
+    last_db_mode_ = 1;
+  } else if (bpat_.usable) {
+    last_db_mode_ = 0;
+    launch_block_pattern_jacobian(bpat_.dev, out, su, st, stream_);
+  } else {
+    launch_row_owner_jacobian(dim_, n_, rb, af, out, su, st, stream_);
+  }
+  residual(side_stream_);
+  MHA_HIP(hipEventRecord(ev_join_, side_stream_));
+  MHA_HIP(hipStreamWaitEvent(stream_, ev_join_, 0));
+}
+
+void AssemblyManager::ensureSideStream() {
+  if (side_stream_) return;
+  MHA_HIP(hipStreamCreateWithFlags(&side_stream_, hipStreamNonBlocking));
+  MHA_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
+  MHA_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
 }
 
 int64_t AssemblyManager::info(const std::string &key) const {

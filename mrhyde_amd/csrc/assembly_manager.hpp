@@ -107,6 +107,7 @@ class AssemblyManager {
  private:
   void requireReady(bool need_graph) const;
   void prepareRowOwner();
+  void tryPrepareRowOwner();
   bool rowOwnerUsable(std::string *why) const;
   void launchRowOwner(bool compute_jacobian, bool overwrite, double *res, double *crs_vals, bool deterministic = false);
   RowBlocksDev rowBlocksDev() const;
@@ -137,6 +138,9 @@ class AssemblyManager {
   DeviceBuffer<uint8_t> d_direct_side_;  // [E][n] (dof order): which incidence of its row the element is
   DeviceBuffer<int32_t> d_direct_diag_;  // [nrows] CRS position of the diagonal of a face row, -1 otherwise
   bool porousDirectUsable();
+  void assembleRowGather(int compute_jacobian, bool overwrite, bool adjoint, bool lump_mass, bool porous_direct,
+                         double *res, double *crs_vals);
+  void assemblePorousDirect(ElemOut o, int compute_jacobian, bool overwrite, double *res, double *crs_vals);
   // database mode of the direct form (uniform mesh, constant coefficients: every element matrix is the same): rows of
   // the same CLASS -- same incident local dofs, same column slots -- are equal, so the element threads store the entries
   // of a few representative rows per class only and line_copy_kernel fills the rest
@@ -221,7 +225,6 @@ class AssemblyManager {
     DeviceBuffer<int32_t> row_ptr, rows, elem_ptr, elems, pair_ptr, pair_off, row_len, seg_ptr, seg_acc, seg_base, seg_len;
     DeviceBuffer<int32_t> blk_rows;  // [touched element of every block][n]: global row of dof j
     DeviceBuffer<int32_t> blk_hdr;   // [block][12] counts and offsets of the block's tables
-    DeviceBuffer<long long> timing;  // profiling aid (MHA_GRO_TIMING)
     DeviceBuffer<int64_t> slot_ptr;
     DeviceBuffer<uint32_t> pairs;
     DeviceBuffer<uint8_t> slot;
@@ -238,9 +241,8 @@ class AssemblyManager {
     int num_patterns = 0, num_roles = 0, num_blocks = 0;
     int64_t mfma_per_assembly = 0;
     BlockPatternDev dev;
-    DeviceBuffer<int32_t> role, seg, wg_seg_ptr, part_ptr, part_hdr, part_lane, rowbase, erec_elem, chunk_tab, wg_seg_ptr_img;
+    DeviceBuffer<int32_t> role, seg, wg_seg_ptr, part_ptr, part_hdr, part_lane, rowbase, erec_elem;
     DeviceBuffer<double> w, erec2;
-    DeviceBuffer<long long> timing;
     // geometry-database mode (one shape in the block): the kernel on one representative block per role + replication
     bool db_mode = false;
     BlockPatternDev dev_rep;  // dev with the segment tables of the representatives
@@ -303,8 +305,10 @@ class AssemblyManager {
   bool timing_ = false;
   double last_ms_ = 0.0;
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr;
-  hipStream_t side_stream_ = nullptr;  // MHA_K1K2_OVERLAP
+  // second stream for kernels that run beside the context's stream (K1 next to K2, the porousMixed database mode)
+  hipStream_t side_stream_ = nullptr;
   hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
+  void ensureSideStream();
 };
 
 }  // namespace mha

@@ -22,15 +22,6 @@
 // All per-block data the kernel reads are block-major with a stride fixed per role (element records, CRS offsets of
 // the rows): every address is computed from the block's ordinal, there are no dependent loads.
 //
-// IMAGE ROLES (round 3).  The CRS rows of a block are odd-length neighbours in memory, so row pieces stored straight
-// from the MFMA registers share their first and last cache line with another wavefront's piece: measured at 3.4 TB/s
-// against 5.3-6.2 TB/s for whole aligned lines (profiles/micro/write_shape.hip).  Where the LDS has room, a role
-// therefore assembles every block as an IMAGE -- the block's runs of consecutive rows, each at its global offset mod
-// 16 entries inside a slot of its own -- and streams it out in aligned 1 KB chunks (one 16-byte store instruction each);
-// only the first and last line of a run are partial.  The LDS for the image comes from keeping the largest W (the
-// rows around a vertex dof) in REGISTERS: its class is cut into units of two column tiles whose 4 x 16 blocks of W sit in
-// at most 56 registers for the life of the segment (REGW units).  Wave 0 of such a role only loads element records.
-//
 // Nothing here assumes a structured mesh: patterns are found by hashing.  A mesh whose blocks share too few patterns
 // reports !usable and the caller keeps the LDS-accumulator row-block kernel.
 #pragma once
@@ -43,14 +34,9 @@
 
 namespace mha {
 
-#ifndef MHA_BP_WAVES
-#define MHA_BP_WAVES 12
-#endif
-constexpr int kBpWaves = MHA_BP_WAVES;  // wavefronts of a persistent workgroup (768 threads, 168 registers each: one workgroup per CU)
+constexpr int kBpWaves = 12;  // wavefronts of a persistent workgroup (768 threads, 168 registers each: one workgroup per CU)
 constexpr int kBpMaxKSteps = 16;   // GEMM depth held in registers: 64 = 9 hexes x 7 or 16 quads x 4
-constexpr int kBpLaneRows = 24;    // per part and lane: [0..15] A offsets (doubles), [16..19] result rows of the lane's registers, [20] tile row lane & 15: run << 20 | CRS offset inside the run, [21] the same row's entry offset inside the block's LDS image (image roles)
-constexpr int kBpStreamWaves = kBpWaves - 1;  // image roles: wave 0 loads the element records, the others stream the image out
-constexpr int kBpChunkInts = 4;    // per 128-entry chunk of an image: run, LDS entry of lane 0, entry of lane 0 relative to the run's aligned start, entries of the run
+constexpr int kBpLaneRows = 24;    // per part and lane: [0..15] A offsets (doubles), [16..19] result rows of the lane's registers, [20] tile row lane & 15: run << 20 | CRS offset inside the run
 constexpr int kBpHdrInts = 12;     // per unit: LDS offset of W, k-steps, column tiles, row length, first tile, tiles, flags, class, 3 words: bit s * 5 + q set = W block (k-step s, tile q) is not zero
 constexpr int kBpRoleInts = 24;    // see block_pattern.cpp
 constexpr int kBpSegInts = 2048;    // (blocks of one segment) x (runs of consecutive rows per block): their CRS offsets sit in LDS
@@ -77,8 +63,7 @@ struct BlockPatternPlan {
   int max_rec_doubles = 0;             // doubles of the largest block's element records
   std::vector<int32_t> role;           // [num_roles][kBpRoleInts]
   std::vector<int32_t> seg;            // [num_segs][4]: role, first block (inside the role), blocks, 0
-  std::vector<int32_t> wg_seg_ptr;     // [num_wgs + 1] -> segments of a workgroup (roles that store from the registers)
-  std::vector<int32_t> wg_seg_ptr_img; // the same for the image roles (a kernel of their own)
+  std::vector<int32_t> wg_seg_ptr;     // [num_wgs + 1] -> segments of a workgroup
   std::vector<int32_t> part_ptr;       // [num_roles][kBpWaves + 1] -> parts of (role, wave)
   std::vector<int32_t> part_hdr;       // [num_parts][kBpHdrInts]
   std::vector<int32_t> part_lane;      // [num_parts][kBpLaneRows][64]
@@ -87,17 +72,14 @@ struct BlockPatternPlan {
   std::vector<int32_t> rowbase;        // role-major, block-major [runs]: CRS offset of the first row of every run of consecutive owned rows
   std::vector<int32_t> runlen;         // role-major [runs]: CRS entries of each run (the same for every block of a role)
   std::vector<int64_t> role_runlen_off;// [num_roles] -> first entry of the role in runlen
-  std::vector<int32_t> chunk_tab;      // image roles: [chunks][kBpChunkInts], role-major
-  int num_image_roles = 0;
   int64_t mfma_per_assembly = 0;       // diagnostics
 };
 
-// seg_blocks > 0: a workgroup's wavefronts meet at a barrier every seg_blocks blocks (their stores stay close in time).
 // rb: row-block partition (any caps); elem_slot: element-major map [e][si][sj] -> position of column lids[e][sj] inside
 // CRS row lids[e][si] (slot_bytes 1 or 2); khat: [nsym + 1][n*n] reference matrices in LID-slot space (last = mass).
 BlockPatternPlan build_block_patterns(const RowBlocks &rb, int n, int nsym, const int32_t *rowptr, const uint8_t *fixed,
                                       const void *elem_slot, int slot_bytes, const double *khat, int num_cus,
-                                      size_t lds_budget_bytes, int max_patterns, int seg_blocks = 0);
+                                      size_t lds_budget_bytes, int max_patterns);
 
 // Walks the plan exactly as the kernel does (workgroup -> wavefront -> part -> block -> MFMA panel) on the host:
 // vals[...] = the CRS values; every entry of an owned row is written exactly once.  factors: [E][ke].

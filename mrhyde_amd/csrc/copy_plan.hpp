@@ -18,10 +18,7 @@ namespace mha {
 
 constexpr int kCopyLineEntries = 16;                     // doubles per 128-byte line
 constexpr int kCopyWaveEntries = 128;                    // one 16-byte store instruction of a wavefront: 8 lines
-#ifndef MHA_COPY_SPAN_LINES
-#define MHA_COPY_SPAN_LINES 32
-#endif
-constexpr int kCopySpanLines = MHA_COPY_SPAN_LINES;      // lines of a work item, a multiple of 8 (profiles/database_copy.md)
+constexpr int kCopySpanLines = 32;                       // lines of a work item, a multiple of 8 (profiles/database_copy.md)
 constexpr int kCopySpanEntries = kCopySpanLines * kCopyLineEntries;
 constexpr int kCopySegRegs = 8;                          // segment records a wavefront holds at once (more: a loop)
 

@@ -143,10 +143,7 @@ struct AffineTables1D {
 // workgroup g takes the elements wg_elems[256 g .. 256 g + 256) (the last group repeats the last element),
 // wg_rows[wg_row_ptr[g] .. wg_row_ptr[g+1]) are the distinct rows their dofs touch, ascending, and
 // loc[(g * n + ib) * 256 + t] is the position in that list of dof ib (BASIS order) of the group's element t.
-#ifndef MHA_K1_THREADS
-#define MHA_K1_THREADS 256
-#endif
-constexpr int kK1PlanThreads = MHA_K1_THREADS;  // elements (= threads) of a workgroup
+constexpr int kK1PlanThreads = 256;  // elements (= threads) of a workgroup
 struct K1PlanDev {
   const int32_t *wg_row_ptr = nullptr;
   const int32_t *wg_rows = nullptr;
@@ -315,16 +312,12 @@ struct SwhFusedOut {
 struct BlockPatternDev {
   int num_wgs = 0, max_w_doubles = 0;
   int max_rec_doubles = 0;             // doubles of the largest block's element records ((T + 1) * 8): LDS image size
-  int dbg = 0;                         // profiling / cross-check aid (env MHA_BP_DBG): 1 plain-load form of every part, 2 no stores, 4 no products
   const double *erec2 = nullptr;       // role-major, block-major element records [T + 1][8]
   const int32_t *rowbase = nullptr;    // role-major, block-major CRS offsets of the owned rows [R]
   const double *w = nullptr;           // LDS images of the roles
   const int32_t *role = nullptr, *seg = nullptr, *wg_seg_ptr = nullptr, *part_ptr = nullptr, *part_hdr = nullptr, *part_lane = nullptr;
-  const int32_t *wg_seg_ptr_img = nullptr;  // segments of the image roles' kernel
-  bool has_direct = true, has_image = false;
-  const int32_t *chunk_tab = nullptr;  // image roles: 64-entry chunks of a block's LDS image (block_pattern.hpp)
+  bool has_direct = true;
   long long nnz = 0;                   // CRS entries (the kernel addresses them with 32-bit byte offsets: nnz < 2^28)
-  long long *timing = nullptr;         // profiling aid (env MHA_BP_TIMING): [num_wgs][16 waves][8] wall-clock stamps (10 ns)
 };
 
 // Destination of the row-owner kernels.

@@ -32,8 +32,8 @@ bool thermal_general_row_owner_supported(int dim, int order, int nq1);
 size_t thermal_general_row_owner_lds(int dim, int order, int nq1, const RowBlocksDev &rb);
 void launch_thermal_general_row_owner(int dim, int order, int nq1, const BlockDev &b, const ThermalDev &ph,
                                       const RowBlocksDev &rb, const uint8_t *slot8, const int32_t *blk_rows,
-                                      const double *gp1d, const int32_t *blk_hdr, long long *timing, const RowOut &out,
-                                      int num_cus, hipStream_t stream);
+                                      const double *gp1d, const int32_t *blk_hdr, const RowOut &out, int num_cus,
+                                      hipStream_t stream);
 
 // mass_apply.hip: applyMassMatrixFree (on the fly / stored dense / database / Sparse3DView) and Sparse3DView's constructor
 void launch_mass_apply_free(const BlockDev &b, const VarLayoutDev &vl, const double *masswts, const double *x, double *y,

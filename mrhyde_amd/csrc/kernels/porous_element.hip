@@ -32,9 +32,7 @@ namespace mha {
 namespace {
 
 constexpr int kPorousThreads = 128;
-#ifndef MHA_POROUS_RES_WAVES
-#define MHA_POROUS_RES_WAVES 2
-#endif
+constexpr int kPorousResWaves = 2;  // waves per SIMD the lean direct build is compiled for
 
 template <int DIM, bool EXPR, bool DOF, bool DIRECT = false, bool RESONLY = false>
 __device__ __forceinline__ void porous_element_body(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp,
@@ -258,7 +256,7 @@ __device__ __forceinline__ void porous_element_body(const BlockDev &b, const Var
           else if (fj == 0) v = au * Bv[fi - 1];
           else v = au * (fj > fi ? A[fi - 1][fj - 1] : A[fj - 1][fi - 1]);
           double *dst = rowv + srow[pos[fj]];
-          if (ow) { if (out.direct_overwrite == 2) __builtin_nontemporal_store(v, dst); else *dst = v; }
+          if (ow) *dst = v;
           else *dst = *dst + v;
         }
       }
@@ -341,7 +339,7 @@ __global__ __launch_bounds__(kPorousThreads) __attribute__((amdgpu_waves_per_eu(
 // the lean build of the direct form: residual parts only (database mode runs it over all elements, the full build over
 // the few elements incident to computed rows)
 template <int DIM>
-__global__ __launch_bounds__(kPorousThreads) __attribute__((amdgpu_waves_per_eu(MHA_POROUS_RES_WAVES))) void porous_element_direct_res_kernel(
+__global__ __launch_bounds__(kPorousThreads) __attribute__((amdgpu_waves_per_eu(kPorousResWaves))) void porous_element_direct_res_kernel(
     BlockDev b, VarLayoutDev vl, PhysParamsDev pp, TimeDev tm, ElemOut out) {
   porous_element_body<DIM, false, true, true, true>(b, vl, pp, tm, out);
 }

@@ -18,7 +18,6 @@
 #include <vector>
 
 #include <cmath>
-#include <cstdlib>
 #include <type_traits>
 
 #include "device_math.hpp"
@@ -65,12 +64,9 @@ __device__ __forceinline__ void apply1d(double *v, const double *T) {
 // (odd strides: conflict-free), instead of 64 different cache lines per load instruction.
 // SMALL: the launcher has checked |freq_d x_d| < 1e5 over the mesh (closed-form source): sines without the full-range fallback
 template <int DIM, int P, bool TR, bool EXPR, bool SMALL>
-#ifndef MHA_K1_WAVES
-#define MHA_K1_WAVES 2
-#endif
-__global__ __launch_bounds__(kK1tThreads, MHA_K1_WAVES) void thermal_affine_residual_kernel(BlockDev b, ThermalDev ph,
+__global__ __launch_bounds__(kK1tThreads, 2) void thermal_affine_residual_kernel(BlockDev b, ThermalDev ph,
                                                                               const double *__restrict__ geo,
-                                                                              const AffineTables1D *__restrict__ tabp, double *res, int dbg) {
+                                                                              const AffineTables1D *__restrict__ tabp, double *res) {
   // The 60 table entries are scalar operands of several hundred FMAs.  Passed by value they sat in 120 SGPRs for the
   // whole kernel (with the other arguments: > 1000 SGPR spill instructions); behind a pointer the compiler fetches them
   // through the scalar cache next to their uses.
@@ -111,7 +107,7 @@ __global__ __launch_bounds__(kK1tThreads, MHA_K1_WAVES) void thermal_affine_resi
 #pragma unroll
   for (int ib = 0; ib < N; ++ib) {
     const int row = L[b.offsets[ib]];
-    const double cu = (dbg & 4) ? 1.0 : tm.u[row];
+    const double cu = tm.u[row];
     double ue = cu;
     if constexpr (TR) {
       const double *cp = tm.u_prev + (size_t)row * tm.nsteps;
@@ -162,7 +158,6 @@ __global__ __launch_bounds__(kK1tThreads, MHA_K1_WAVES) void thermal_affine_resi
     for (int c = 0; c < DIM; ++c)
       if (r != c && J[r][c] != 0.0) separable = false;
   double s1d[DIM][M];
-  if (dbg & 2) separable = false;
   if (__builtin_amdgcn_ballot_w64(!separable) == 0) {
 #pragma unroll
     for (int d = 0; d < DIM; ++d)
@@ -240,24 +235,20 @@ __global__ __launch_bounds__(kK1tThreads, MHA_K1_WAVES) void thermal_affine_resi
   int rowv[N];
 #pragma unroll
   for (int ib = 0; ib < N; ++ib) rowv[ib] = active ? L[b.offsets[ib]] : -2 - lane;
-  if (!(dbg & 8)) {
 #pragma unroll
-    for (int il = 0; il < N; il += M) {  // dof index x fastest: il = (0, iy, iz), ir = (M-1, iy, iz)
-      const int ir = il + M - 1;
-      const int prow = __shfl_up(rowv[ir], 1);
-      const double pw = __shfl_up(W[ir], 1);
-      const bool take = lane > 0 && prow == rowv[il];
-      if (take) W[il] += pw;
-      const int given = __shfl_down((int)take, 1);
-      if (lane < 63 && given) rowv[ir] = -1;  // the next lane carries this node
-    }
+  for (int il = 0; il < N; il += M) {  // dof index x fastest: il = (0, iy, iz), ir = (M-1, iy, iz)
+    const int ir = il + M - 1;
+    const int prow = __shfl_up(rowv[ir], 1);
+    const double pw = __shfl_up(W[ir], 1);
+    const bool take = lane > 0 && prow == rowv[il];
+    if (take) W[il] += pw;
+    const int given = __shfl_down((int)take, 1);
+    if (lane < 63 && given) rowv[ir] = -1;  // the next lane carries this node
   }
-  if (!(dbg & 1)) {
 #pragma unroll
-    for (int ib = 0; ib < N; ++ib) {
-      const int row = rowv[ib];
-      if (row >= 0 && !(b.fixed && b.fixed[row])) atomicAdd(res + row, -W[ib]);
-    }
+  for (int ib = 0; ib < N; ++ib) {
+    const int row = rowv[ib];
+    if (row >= 0 && !(b.fixed && b.fixed[row])) atomicAdd(res + row, -W[ib]);
   }
 }
 
@@ -281,7 +272,7 @@ __global__ __launch_bounds__(kK1tThreads, MHA_K1_WAVES) void thermal_affine_resi
 template <int DIM, int P, bool TR, bool EXPR, bool SMALL, bool SEPK>
 __global__ __launch_bounds__(kK1wThreads, (TR || EXPR || !SEPK) ? 2 : 3) void thermal_affine_residual_wg_kernel(
     BlockDev b, ThermalDev ph, const double *__restrict__ geo, const AffineTables1D *__restrict__ tabp, K1PlanDev pl,
-    double *res, int dbg) {
+    double *res) {
   const AffineTables1D &tab = *tabp;
   constexpr int M = P + 1, N = cpow(M, DIM);
   extern __shared__ double s_tab[];  // [max_rows] seeded u, then the accumulated -r; TR: [max_rows] u_dot behind it;
@@ -380,7 +371,6 @@ __global__ __launch_bounds__(kK1wThreads, (TR || EXPR || !SEPK) ? 2 : 3) void th
     if constexpr (DIM == 3) apply1d<DIM, M, DIM - 1, true>(Ud, tab.phi);
   }
   const double kap = ph.diff.amp, rc = ph.rho.amp * ph.cp.amp;  // element-wise constants on this path
-  if (dbg & 2) separable = false;
   const bool all_sep = SEPK || __builtin_amdgcn_ballot_w64(!separable) == 0;
   double s1d[DIM][M];
   if (all_sep) {
@@ -469,11 +459,9 @@ __global__ __launch_bounds__(kK1wThreads, (TR || EXPR || !SEPK) ? 2 : 3) void th
   __syncthreads();
   // ---- E. one atomic per listed row, fixed rows skipped; the row ids come from LDS (a load from memory here would be
   //      a latency nothing hides: 12 us of the kernel's 74 when the ids and flags were fetched again) ----
-  if (!(dbg & 1)) {
-    for (int i = tid; i < nr; i += kK1wThreads) {
-      const int row = s_row[i];
-      if (row >= 0) atomicAdd(res + row, s_tab[i]);
-    }
+  for (int i = tid; i < nr; i += kK1wThreads) {
+    const int row = s_row[i];
+    if (row >= 0) atomicAdd(res + row, s_tab[i]);
   }
 }
 
@@ -499,7 +487,6 @@ void launch_t(const BlockDev &b, const ThermalDev &ph, const double *geo, const 
               double *res, bool small_args, hipStream_t stream) {
   if (b.e_count <= 0) return;
   const AffineTables1D *tab = device_copy(tab_host);
-  static const int dbg_wg = [] { const char *m = std::getenv("MHA_K1_DBG"); return m ? std::atoi(m) : 0; }();
   if (plan && plan->loc) {  // workgroup-merged form (the plan covers the block's elements from e_begin = 0)
     MHA_REQUIRE(b.e_begin == 0 && b.e_count == plan->num_elems, MHA_ERR_INVALID, "K1 plan: element range mismatch");
     const int grid = (b.e_count + kK1wThreads - 1) / kK1wThreads;
@@ -507,13 +494,13 @@ void launch_t(const BlockDev &b, const ThermalDev &ph, const double *geo, const 
     const size_t lds = sizeof(double) * (size_t)plan->max_rows * (tr ? 2 : 1) + sizeof(int) * (size_t)plan->max_rows + sizeof(uint16_t) * cpow(P + 1, DIM) * kK1wThreads;
     auto go = [&](auto kern) {
       if (lds > 64 * 1024) MHA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(kK1wThreads), lds, stream, b, ph, geo, tab, *plan, res, dbg_wg);
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(kK1wThreads), lds, stream, b, ph, geo, tab, *plan, res);
     };
     const bool sinprod = ph.source.kind != MHA_FUNC_CONSTANT && ph.source.kind != MHA_FUNC_IP_ARRAY && ph.source.kind != MHA_FUNC_EXPRESSION;
     if (has_expression(ph.source)) {
       if (tr) go(thermal_affine_residual_wg_kernel<DIM, P, true, true, false, false>);
       else go(thermal_affine_residual_wg_kernel<DIM, P, false, true, false, false>);
-    } else if (plan->axis_aligned && sinprod && !(dbg_wg & 2)) {
+    } else if (plan->axis_aligned && sinprod) {
       if (small_args) {
         if (tr) go(thermal_affine_residual_wg_kernel<DIM, P, true, false, true, true>);
         else go(thermal_affine_residual_wg_kernel<DIM, P, false, false, true, true>);
@@ -533,8 +520,7 @@ void launch_t(const BlockDev &b, const ThermalDev &ph, const double *geo, const 
   }
   const int grid = (b.e_count + kK1tThreads - 1) / kK1tThreads;  // a wavefront takes 64 consecutive elements
   const bool tr = ph.time.transient != 0;
-  static const int dbg = [] { const char *m = std::getenv("MHA_K1_DBG"); return m ? std::atoi(m) : 0; }();  // profiling aid: 1 no atomics, 2 general source evaluation, 4 no gather
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kK1tThreads), 0, stream, b, ph, geo, tab, res, dbg); };
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kK1tThreads), 0, stream, b, ph, geo, tab, res); };
   if (has_expression(ph.source)) {
     if (tr) go(thermal_affine_residual_kernel<DIM, P, true, true, false>);
     else go(thermal_affine_residual_kernel<DIM, P, false, true, false>);

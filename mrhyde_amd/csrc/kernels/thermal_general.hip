@@ -52,23 +52,11 @@ struct GK {
   static constexpr int QC = NQ < 9 ? NQ : 9;      // integration points per GEMM chunk
   static constexpr int NCH = (NQ + QC - 1) / QC;
   static constexpr int KC = QC * DIM + (TR ? QC : 0);  // GEMM depth of one chunk (+ mass columns)
-#ifndef MHA_TG_MFMA
-#define MHA_TG_MFMA 1
-#endif
-#ifndef MHA_TG_STOP
-#define MHA_TG_STOP 9  // profiling aid (profiles/tg_ablate.sh): leave the kernel after phase 1, 2, 3 or the product (4)
-#endif
-  static constexpr bool MF = MHA_TG_MFMA && N > 16;  // Jacobian product on the matrix cores (2 x 2 tiles of 16 x 16)
-#ifndef MHA_TG_QM
-#define MHA_TG_QM 8
-#endif
-  static constexpr int QM = MHA_TG_QM;            // points per MFMA chunk: QM * DIM rows of P, a multiple of 4
+  static constexpr bool MF = N > 16;              // Jacobian product on the matrix cores (2 x 2 tiles of 16 x 16)
+  static constexpr int QM = 8;                    // points per MFMA chunk: QM * DIM rows of P, a multiple of 4
   static constexpr int PR = QM * DIM;             // rows of the MFMA P panel
   static constexpr int PW = 32;                   // its width (dofs, zero padded)
-#ifndef MHA_TG_EPB
-#define MHA_TG_EPB 4
-#endif
-  static constexpr int EPB = MHA_TG_EPB;          // elements (waves) per workgroup
+  static constexpr int EPB = 4;                   // elements (waves) per workgroup
   static constexpr int NT = EPB * 64;             // threads per workgroup
   // shared tables (doubles)
   static constexpr int S_GT = 0;                  // Ghat^T  [NQ*DIM][NP]
@@ -89,11 +77,9 @@ struct GK {
   static constexpr int REC = (O_PT + (MF ? PR * PW : KC * NP) + 1) / 2 * 2;
 };
 
-#ifndef MHA_TG_MINW
-#define MHA_TG_MINW 2
-#endif
+constexpr int kTgMinWaves = 2;  // __launch_bounds__: at least this many waves per SIMD
 template <int DIM, int P, int NQ1, bool TR, bool EXPR>
-__global__ __launch_bounds__((GK<DIM, P, NQ1, TR>::NT), MHA_TG_MINW) void thermal_general_element_kernel(BlockDev b, ThermalDev ph, AffineDev af,
+__global__ __launch_bounds__((GK<DIM, P, NQ1, TR>::NT), kTgMinWaves) void thermal_general_element_kernel(BlockDev b, ThermalDev ph, AffineDev af,
                                                                        const uint8_t *__restrict__ slot8,
                                                                        const uint16_t *__restrict__ slot16, ElemOut out) {
   using S = GK<DIM, P, NQ1, TR>;
@@ -190,7 +176,6 @@ __global__ __launch_bounds__((GK<DIM, P, NQ1, TR>::NT), MHA_TG_MINW) void therma
     }
   }
   wave_lds_sync();  // the record is private to this wavefront
-  if (MHA_TG_STOP == 1) continue;
 
   // ---- 2. fields at the integration points, point-wise residual data (lane = q) ----
   if (active) {
@@ -219,7 +204,6 @@ __global__ __launch_bounds__((GK<DIM, P, NQ1, TR>::NT), MHA_TG_MINW) void therma
     }
   }
   wave_lds_sync();
-  if (MHA_TG_STOP == 2) continue;
 
   // ---- 3. residual rows (lane = basis dof) ----
   if (active) {
@@ -241,7 +225,7 @@ __global__ __launch_bounds__((GK<DIM, P, NQ1, TR>::NT), MHA_TG_MINW) void therma
       }
     }
   }
-  if (out.compute_jacobian <= 0 || MHA_TG_STOP == 3) continue;  // uniform
+  if (out.compute_jacobian <= 0) continue;  // uniform
 
   const double au = tm.alpha_u, at = tm.alpha_t;
   if constexpr (S::MF) {
@@ -313,10 +297,6 @@ __global__ __launch_bounds__((GK<DIM, P, NQ1, TR>::NT), MHA_TG_MINW) void therma
           const int nq = (q0 + S::PR <= NQ) ? S::PR : NQ - q0;
           product(NQ * DIM + q0, (nq + 3) & ~3);
         }
-      }
-      if (MHA_TG_STOP == 4) {  // keep the product alive without the stores
-        if (acc[0][0][0] + acc[0][1][1] + acc[1][0][2] + acc[1][1][3] == 12345.678) out.local_J[0] = 1.0;
-        continue;
       }
       // ---- 5m. store / scatter the tiles: 16 consecutive columns per row and register ----
 #pragma unroll

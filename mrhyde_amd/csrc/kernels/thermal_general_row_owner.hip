@@ -115,21 +115,14 @@ __host__ __device__ inline RgLds rg_layout(int T, int rows, int acc, int pairs, 
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
-#ifndef MHA_RG_FETCH_WAVES
-#define MHA_RG_FETCH_WAVES 2
-#endif
 constexpr int kRgSlotRegs = 2;  // uint4 per fetching thread: pairs * n <= 2 * 256 * 16 bytes
 
-template <int DIM, int P, int NQ1, bool TR, bool EXPR, bool TIMING>
+template <int DIM, int P, int NQ1, bool TR, bool EXPR>
 __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev b, ThermalDev ph, RowBlocksDev rb,
                                                                         const uint8_t *__restrict__ slot8,
                                                                         const int32_t *__restrict__ blk_rows,
                                                                         const double *__restrict__ gp1d,
-                                                                        const int32_t *__restrict__ blk_hdr, RowOut out,
-                                                                        int dbg_arg, long long *timing) {
-  const int dbg = TIMING ? dbg_arg : 0;  // the ablation switches exist in the profiling build only
-  // dbg (env MHA_GRO_DBG, profiling only -- results are wrong): 1 no field / geometry phases, 2 no residual sums,
-  // 4 no products, 8 no LDS adds of the tiles, 16 no CRS stores, 32 no fetch of the next block (stale data)
+                                                                        const int32_t *__restrict__ blk_hdr, RowOut out) {
   using S = RG<DIM, P, NQ1, TR>;
   constexpr int N = S::N, NQ = S::NQ, NQ4 = S::NQ4, NN = S::NN, NSYM = S::NSYM, QG = S::QG, KSM = S::KSM;
   constexpr int CT = S::CT, NT = S::NT, NW = S::NW;
@@ -178,7 +171,7 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
   // the other table buffer, the row ids of the touched elements' dofs into s_ids.  Stage B (once the scratch is free,
   // after G2, while the other waves start on the tiles): vertices and seeded solution values through those ids.
   // Every load of a stage is issued before its first store.
-  constexpr int NF = MHA_RG_FETCH_WAVES;  // waves that load from global memory; the other NW - NF store to it
+  constexpr int NF = 2;  // waves that load from global memory; the other NW - NF store to it
   constexpr int PT = NF * 64;
   constexpr int KA = (256 + PT - 1) / PT;                         // table entries per fetching thread (every table holds <= 256)
   constexpr int MAXT = (DIM == 3) ? 27 : 25;            // touched elements of a block (host caps)
@@ -296,11 +289,8 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
     if (fetcher) MHA_RG_STAGE_B(s_hdr[0], base + L.tab[0])
   }
   lds_barrier();
-  long long tacc[6] = {0, 0, 0, 0, 0, 0}, tprev = 0;
-#define MHA_RG_STAMP(k_) if constexpr (TIMING) { const long long now = __builtin_readcyclecounter(); tacc[k_] += now - tprev; tprev = now; }
 
   for (int blk = blockIdx.x; blk < rb.num_blocks; blk += gridDim.x) {
-    if constexpr (TIMING) tprev = __builtin_readcyclecounter();
     int hc[HW], hn[HW];
 #pragma unroll
     for (int k = 0; k < 10; ++k) {
@@ -309,7 +299,7 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
     }
     const int T = hc[1], NP = hc[3], NR = hc[5], NS = hc[7];
     const int next = blk + gridDim.x;
-    const bool prefetch = fetcher && next < rb.num_blocks && !(dbg & 32);
+    const bool prefetch = fetcher && next < rb.num_blocks;
     char *tb = base + L.tab[cur], *tbnext = base + L.tab[cur ^ 1];
     const uint32_t *s_pairs = reinterpret_cast<const uint32_t *>(tb + L.t_pairs);
     const int *s_segs = reinterpret_cast<const int *>(tb + L.t_segs), *s_rows = reinterpret_cast<const int *>(tb + L.t_rows);
@@ -322,7 +312,7 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
     // ---- G1 (all waves, the fetching ones join late). fields on the matrix cores: gu[t][(a,q)] = sum_j ue[t][j] dhat_a N_j(q) -> s_F,
     //      tt[t][q] = sum_j ud[t][j] N_j(q) -> s_S; the fetching waves issue stage A of the next block first
     if (prefetch) MHA_RG_STAGE_A_LOAD(hn)
-    if (!(dbg & 1)) {
+    {
       constexpr int KJ = (N + 3) / 4, CG = (DIM * NQ4 + 15) / 16, CS = TR ? (NQ4 + 15) / 16 : 0;
       const int RT = (T + 15) / 16;
       for (;;) {  // jobs are taken as the waves become free (the fetching waves join after issuing stage A)
@@ -362,10 +352,9 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
     if (prefetch) MHA_RG_STAGE_A_STORE(hn, tbnext)
     if (tid < HW) s_hdr[cur][tid] = hdr2;
     if (tid == 0) { s_job = 0; s_tile = 0; }   // fields done, tiles not started: both counters are idle here
-    MHA_RG_STAMP(0)
 
     // ---- G2. geometry, coefficients, point-wise residual data at (touched element, point) ----
-    for (int item = tid; item < ((dbg & 1) ? 0 : T * NQ); item += NT) {
+    for (int item = tid; item < T * NQ; item += NT) {
       const int t = item / NQ, q = item - t * NQ;
       const int e = s_elems[t];
       const double *xn = s_xn + t * NN * DIM;
@@ -430,14 +419,12 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
       if constexpr (TR) s_M[t * NQ4 + q] = tm.alpha_t * rc * w;
     }
     lds_barrier();  // point data complete; the scratch (vertices, seeded values) is dead
-    MHA_RG_STAMP(1)
 
     // ---- T. stage B of the next block (fetching waves), Jacobian rows + residual entries of the pairs ----
     if (prefetch) {
       MHA_RG_SLOT_LOAD(hn)
       MHA_RG_STAGE_B(hn, tbnext)
     }
-    MHA_RG_STAMP(2)
     auto tiles = [&](auto jac_c) {
       constexpr bool JAC = decltype(jac_c)::value;
       // B[k = lane>>4 (+4s)][col = lane&15] of k-step s = (b, four points) is read from the Ghat table for every product (one
@@ -471,10 +458,9 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
         const double *aM = s_M + t * NQ4 + g4, *aN = sh + S::S_NV + i * NQ4 + g4;
         v4d c0 = {0.0, 0.0, 0.0, 0.0}, c1 = {0.0, 0.0, 0.0, 0.0};
         double rp = 0.0;
-        if (!(dbg & 4)) {
-          // operands of point group qg+1 are requested before the products of group qg are issued: two register sets.
-          // The fences keep that order (left alone, the scheduler hoists every read of the tile to the top: scratch)
-          double G3[2][DIM], D6[2][NSYM], F3[2][DIM], S1[2], NV[2], M1[2], BB[2][DIM][2];
+        // operands of point group qg+1 are requested before the products of group qg are issued: two register sets.
+        // The fences keep that order (left alone, the scheduler hoists every read of the tile to the top: scratch)
+        double G3[2][DIM], D6[2][NSYM], F3[2][DIM], S1[2], NV[2], M1[2], BB[2][DIM][2];
 #define MHA_RG_LOAD(qg_, s_)                                                                 \
   {                                                                                          \
     _Pragma("unroll") for (int aa = 0; aa < DIM; ++aa) G3[s_][aa] = aG[(aa * QG + (qg_)) * 64 * CT]; \
@@ -489,40 +475,37 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
       if constexpr (TR) M1[s_] = aM[4 * (qg_)];                                              \
     }                                                                                        \
   }
-          MHA_RG_LOAD(0, 0)
+        MHA_RG_LOAD(0, 0)
 #pragma unroll
-          for (int qg = 0; qg < QG; ++qg) {
-            const int sb = qg & 1;
-            __builtin_amdgcn_sched_barrier(0);
-            if (qg + 1 < QG) MHA_RG_LOAD(qg + 1, (qg + 1) & 1)
-            __builtin_amdgcn_sched_barrier(0);
-            if (!(dbg & 2)) {
-              rp += S1[sb] * NV[sb];
+        for (int qg = 0; qg < QG; ++qg) {
+          const int sb = qg & 1;
+          __builtin_amdgcn_sched_barrier(0);
+          if (qg + 1 < QG) MHA_RG_LOAD(qg + 1, (qg + 1) & 1)
+          __builtin_amdgcn_sched_barrier(0);
+          rp += S1[sb] * NV[sb];
 #pragma unroll
-              for (int aa = 0; aa < DIM; ++aa) rp += F3[sb][aa] * G3[sb][aa];
+          for (int aa = 0; aa < DIM; ++aa) rp += F3[sb][aa] * G3[sb][aa];
+          if constexpr (JAC) {
+#pragma unroll
+            for (int bb = 0; bb < DIM; ++bb) {
+              double a = 0.0;
+#pragma unroll
+              for (int aa = 0; aa < DIM; ++aa) a += D6[sb][sym_index(DIM, bb, aa)] * G3[sb][aa];
+              c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, BB[sb][bb][0], c0, 0, 0, 0);
+              if constexpr (CT == 2) c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, BB[sb][bb][1], c1, 0, 0, 0);
             }
-            if constexpr (JAC) {
-#pragma unroll
-              for (int bb = 0; bb < DIM; ++bb) {
-                double a = 0.0;
-#pragma unroll
-                for (int aa = 0; aa < DIM; ++aa) a += D6[sb][sym_index(DIM, bb, aa)] * G3[sb][aa];
-                c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, BB[sb][bb][0], c0, 0, 0, 0);
-                if constexpr (CT == 2) c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, BB[sb][bb][1], c1, 0, 0, 0);
-              }
-              if constexpr (TR) {
-                const double a = M1[sb] * NV[sb];
-                c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bm[qg][0], c0, 0, 0, 0);
-                if constexpr (CT == 2) c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bm[qg][CT - 1], c1, 0, 0, 0);
-              }
+            if constexpr (TR) {
+              const double a = M1[sb] * NV[sb];
+              c0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bm[qg][0], c0, 0, 0, 0);
+              if constexpr (CT == 2) c1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Bm[qg][CT - 1], c1, 0, 0, 0);
             }
           }
-#undef MHA_RG_LOAD
         }
+#undef MHA_RG_LOAD
         // residual entry of the pair: sum over the four lane groups; the global vector receives -res.val() (scatterRes)
         rp += __shfl_xor(rp, 16);
         rp += __shfl_xor(rp, 32);
-        if (g4 == 0 && pmine < NP && !(dbg & 2)) {
+        if (g4 == 0 && pmine < NP) {
           if (!JAC && out.ordered) acc[pmine] = -rp;  // deterministic mode: the row's owner sums its pairs in pair order below
           else atomicAdd(&racc[o], -rp);
         }
@@ -531,7 +514,7 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             const int pp = tile * 16 + g4 + 4 * u;
-            if (pp < NP && !(dbg & 8)) {
+            if (pp < NP) {
               const int po = s_pairoff[pp];
               const uint8_t *sl = s_slot + pp * N;
               if (l15 < N) atomicAdd(&acc[po + sl[s_offs[l15]]], c0[u]);
@@ -544,9 +527,7 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
       }
     };
     if (jac) tiles(std::true_type()); else tiles(std::false_type());
-    MHA_RG_STAMP(3)
     lds_barrier();
-    MHA_RG_STAMP(4)
     if (prefetch) MHA_RG_SLOT_STORE(hn)  // nobody reads the slot table again before the next block's T
 
     // ---- S. stream the finished rows in contiguous runs; what has been read is zeroed for the next block ----
@@ -555,7 +536,7 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
     // through one in-order counter (vmcnt), so a wave that has just streamed out CRS rows would wait for the last of
     // those writes to be acknowledged before it could use the first value it loads for the next block.
     if (jac && !fetcher) {
-      for (int sg = wave - NF; sg < ((dbg & 16) ? 0 : NS); sg += NW - NF) {
+      for (int sg = wave - NF; sg < NS; sg += NW - NF) {
         int len = s_segs[2 * rb.lds_segs + sg];
         const bool fixed_run = len < 0;  // run of fixed rows: zeros when storing, untouched when accumulating
         if (fixed_run) len = -len;
@@ -594,13 +575,8 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
     }
     // no barrier here: the next block's field phase touches neither the accumulators nor this block's tables, and the
     // first barrier of the next block orders this store phase before anything that does
-    MHA_RG_STAMP(5)
     cur ^= 1;
   }
-  if constexpr (TIMING)
-    if (lane == 0)
-      for (int k = 0; k < 6; ++k) timing[((size_t)blockIdx.x * NW + wave) * 8 + k] = tacc[k];
-#undef MHA_RG_STAMP
 #undef MHA_RG_STAGE_A_LOAD
 #undef MHA_RG_STAGE_A_STORE
 #undef MHA_RG_SLOT_LOAD
@@ -610,7 +586,7 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
 
 template <int DIM, int P, int NQ1>
 void launch_rg(const BlockDev &b, const ThermalDev &ph, RowBlocksDev rb, const uint8_t *slot8, const int32_t *blk_rows,
-               const double *gp1d, const int32_t *blk_hdr, long long *timing, const RowOut &out, int num_cus,
+               const double *gp1d, const int32_t *blk_hdr, const RowOut &out, int num_cus,
                hipStream_t stream) {
   const bool tr = ph.time.transient != 0, expr = has_expression(ph);
   rb.lds_acc = (rb.lds_acc + 1) / 2 * 2;
@@ -621,22 +597,16 @@ void launch_rg(const BlockDev &b, const ThermalDev &ph, RowBlocksDev rb, const u
   auto go = [&](auto kern, size_t lds) {
     MHA_REQUIRE(lds <= 160 * 1024, MHA_ERR_INVALID, "general row-owner kernel needs " << lds << " B of LDS (> 160 KiB)");
     MHA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    static const int dbg = [] { const char *m = std::getenv("MHA_GRO_DBG"); return m ? std::atoi(m) : 0; }();
-    hipLaunchKernelGGL(kern, dim3(std::min(rb.num_blocks, num_cus)), dim3(512), lds, stream, b, ph, rb, slot8, blk_rows, gp1d, blk_hdr, out, dbg, timing);
+    hipLaunchKernelGGL(kern, dim3(std::min(rb.num_blocks, num_cus)), dim3(512), lds, stream, b, ph, rb, slot8, blk_rows, gp1d, blk_hdr, out);
   };
-  if (timing) {  // profiling build of the two plain-coefficient variants only
-    if (tr) go(thermal_general_row_owner_kernel<DIM, P, NQ1, true, false, true>,
-               rg_layout<DIM, P, NQ1, true>(rb.lds_elems, rb.lds_rows, rb.lds_acc, rb.lds_pairs, rb.lds_segs).total);
-    else go(thermal_general_row_owner_kernel<DIM, P, NQ1, false, false, true>,
-            rg_layout<DIM, P, NQ1, false>(rb.lds_elems, rb.lds_rows, rb.lds_acc, rb.lds_pairs, rb.lds_segs).total);
-  } else if (tr) {
+  if (tr) {
     const size_t lds = rg_layout<DIM, P, NQ1, true>(rb.lds_elems, rb.lds_rows, rb.lds_acc, rb.lds_pairs, rb.lds_segs).total;
-    if (expr) go(thermal_general_row_owner_kernel<DIM, P, NQ1, true, true, false>, lds);
-    else go(thermal_general_row_owner_kernel<DIM, P, NQ1, true, false, false>, lds);
+    if (expr) go(thermal_general_row_owner_kernel<DIM, P, NQ1, true, true>, lds);
+    else go(thermal_general_row_owner_kernel<DIM, P, NQ1, true, false>, lds);
   } else {
     const size_t lds = rg_layout<DIM, P, NQ1, false>(rb.lds_elems, rb.lds_rows, rb.lds_acc, rb.lds_pairs, rb.lds_segs).total;
-    if (expr) go(thermal_general_row_owner_kernel<DIM, P, NQ1, false, true, false>, lds);
-    else go(thermal_general_row_owner_kernel<DIM, P, NQ1, false, false, false>, lds);
+    if (expr) go(thermal_general_row_owner_kernel<DIM, P, NQ1, false, true>, lds);
+    else go(thermal_general_row_owner_kernel<DIM, P, NQ1, false, false>, lds);
   }
   MHA_HIP(hipGetLastError());
 }
@@ -661,12 +631,12 @@ size_t thermal_general_row_owner_lds(int dim, int order, int nq1, const RowBlock
 
 void launch_thermal_general_row_owner(int dim, int order, int nq1, const BlockDev &b, const ThermalDev &ph,
                                       const RowBlocksDev &rb, const uint8_t *slot8, const int32_t *blk_rows,
-                                      const double *gp1d, const int32_t *blk_hdr, long long *timing, const RowOut &out, int num_cus,
+                                      const double *gp1d, const int32_t *blk_hdr, const RowOut &out, int num_cus,
                hipStream_t stream) {
   if (rb.num_blocks <= 0) return;
   MHA_REQUIRE(rb.lds_acc < 65536, MHA_ERR_INVALID, "general row-owner kernel: accumulator offsets must fit 16 bits");
 #define MHA_RG_GO(D_, P_, Q_) \
-  if (dim == D_ && order == P_ && nq1 == Q_) return launch_rg<D_, P_, Q_>(b, ph, rb, slot8, blk_rows, gp1d, blk_hdr, timing, out, num_cus, stream);
+  if (dim == D_ && order == P_ && nq1 == Q_) return launch_rg<D_, P_, Q_>(b, ph, rb, slot8, blk_rows, gp1d, blk_hdr, out, num_cus, stream);
   MHA_RG_GO(2, 1, 2) MHA_RG_GO(2, 2, 3) MHA_RG_GO(2, 3, 4) MHA_RG_GO(2, 4, 5) MHA_RG_GO(3, 1, 2) MHA_RG_GO(3, 2, 3)
 #undef MHA_RG_GO
   MHA_REQUIRE(false, MHA_ERR_INVALID, "general row-owner kernel: unsupported (dim, order, points/dir)");

@@ -9,7 +9,7 @@
 //      the Jacobian volume).  Element geometry {detJ*J^{-1}J^{-T}, detJ, J, centroid} comes from a
 //      160-byte per-element cache filled once per mesh (affine_geometry_kernel).
 //
-//  K2  row_owner_jacobian_kernel       (row-owner, one workgroup per row block, row_blocks.hpp)
+//  K2  row_owner_jacobian_persistent_kernel  (row-owner, persistent workgroups over the row blocks, row_blocks.hpp)
 //      every CRS row is produced by exactly one workgroup: it walks the elements incident to its rows,
 //      accumulates their contributions in LDS (ds_add_f64) and streams whole rows to HBM with plain
 //      coalesced stores.  Lane (si,sj) keeps "its" entries of the reference tables in registers:
@@ -25,11 +25,9 @@
 // 937-1062; src/interfaces/discretizationInterface.cpp:732-776, 898-981; src/physics/thermal.cpp:71-165).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <string>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "device_math.hpp"
 #include "launch.hpp"
@@ -314,103 +312,6 @@ __global__ __launch_bounds__(256) void build_erec_kernel(RowBlocksDev rb, const 
   }
 }
 
-template <int DIM, int N, int NT, typename SlotT>
-__global__ __launch_bounds__(NT, (NT == 384 ? 6 : 1)) void row_owner_jacobian_kernel(
-    RowBlocksDev rb, const double *__restrict__ erec, const double *__restrict__ khat,
-    const uint4 *__restrict__ slot16, const uint16_t *__restrict__ pair_off16, RowOut out, double su, double st) {
-  constexpr int NSYM = DIM * (DIM + 1) / 2, NN2 = N * N, NITER = (NN2 + NT - 1) / NT;
-  static_assert(N <= 32, "ownership masks are 32 bits wide");
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const int blk = rb.block_list ? rb.block_list[blockIdx.x] : blockIdx.x;
-  const int t0 = rb.elem_ptr[blk], T = rb.elem_ptr[blk + 1] - t0;
-  const int p0 = rb.pair_ptr[blk], NP = rb.pair_ptr[blk + 1] - p0;
-  const int A = rb.acc_size[blk];
-
-  extern __shared__ double smem[];
-  double *acc = smem;                                                    // [lds_acc], lds_acc even
-  SlotT *s_slot = reinterpret_cast<SlotT *>(acc + rb.lds_acc);           // [lds_pairs*N -> 16 B]
-  uint16_t *s_pairoff = reinterpret_cast<uint16_t *>(reinterpret_cast<char *>(s_slot) +
-                                                     ((size_t)rb.lds_pairs * N * sizeof(SlotT) + 15) / 16 * 16);
-
-  // this lane's reference table entries, kept in registers for the whole block; the LID slots (si)
-  // this WAVE covers, as a bit mask, for the wave-level skip
-  double kh[NITER][NSYM + 1];
-  unsigned my_bit[NITER], my_low[NITER];
-  int my_sj[NITER];
-  unsigned wave_si = 0u;
-#pragma unroll
-  for (int it = 0; it < NITER; ++it) {
-    const int idx = tid + it * NT;
-    const int si = (idx < NN2) ? idx / N : 0;
-    my_bit[it] = (idx < NN2) ? (1u << si) : 0u;
-    my_low[it] = (1u << si) - 1u;
-    my_sj[it] = idx - si * N;
-#pragma unroll
-    for (int k = 0; k <= NSYM; ++k)  // the run-time scale factors are folded into the table entries once
-      kh[it][k] = (idx < NN2) ? (k < NSYM ? su : st) * khat[k * NN2 + idx] : 0.0;
-    const int lo = wave * 64 + it * NT, hi = min(lo + 63, NN2 - 1);
-    if (lo < NN2) {
-      const int a = lo / N, c = hi / N;
-      wave_si |= (c >= 31 ? 0xffffffffu : ((1u << (c + 1)) - 1u)) & ~((1u << a) - 1u);
-    }
-  }
-
-  // ---- block tables into LDS, zero the accumulators ----
-  for (int p = tid; p < NP; p += NT) s_pairoff[p] = pair_off16[p0 + p];
-  {
-    const uint4 *src = slot16 + rb.slot_ptr[blk] / 16;
-    uint4 *dst = reinterpret_cast<uint4 *>(s_slot);
-    const int n16 = (int)((rb.slot_ptr[blk + 1] - rb.slot_ptr[blk]) / 16);
-    for (int i = tid; i < n16; i += NT) dst[i] = src[i];
-  }
-  {
-    double2 *a2 = reinterpret_cast<double2 *>(acc);
-    for (int i = tid; i < (A + 1) / 2; i += NT) a2[i] = make_double2(0.0, 0.0);
-  }
-  __syncthreads();
-
-  // ---- contributions: lane (si,sj) walks the block's elements; the 64-byte element record is one
-  //      wave-uniform (scalar) load from the block-major table; a wave skips elements none of whose
-  //      owned rows fall into its si range ----
-  for (int t = 0; t < T; ++t) {
-    const double *E = erec + (size_t)(t0 + t) * kERec;
-    const double mp = E[7];
-    const unsigned mask = (unsigned)__double2loint(mp);
-    if ((mask & wave_si) == 0u) continue;
-    const int pb = __double2hiint(mp);
-    double g[NSYM + 1];
-#pragma unroll
-    for (int k = 0; k <= NSYM; ++k) g[k] = E[k];
-#pragma unroll
-    for (int it = 0; it < NITER; ++it) {
-      if (mask & my_bit[it]) {
-        const int p = pb + __popc(mask & my_low[it]);
-        double v = g[NSYM] * kh[it][NSYM];
-#pragma unroll
-        for (int k = 0; k < NSYM; ++k) v += g[k] * kh[it][k];
-        atomicAdd(&acc[(int)s_pairoff[p] + (int)s_slot[p * N + my_sj[it]]], v);
-      }
-    }
-  }
-  __syncthreads();
-
-  // ---- stream the finished rows to HBM, one contiguous run of rows at a time ----
-  for (int s = rb.seg_ptr[blk]; s < rb.seg_ptr[blk + 1]; ++s) {
-    int len = rb.seg_len[s];
-    if (len < 0) {  // run of fixed rows: zeros when storing, untouched when accumulating
-      if (!out.overwrite) continue;
-      len = -len;
-    }
-    double *dst = out.vals + rb.seg_base[s];
-    const double *src = acc + rb.seg_acc[s];
-    if (out.overwrite) {
-      for (int k = tid; k < len; k += NT) dst[k] = src[k];
-    } else {
-      for (int k = tid; k < len; k += NT) dst[k] += src[k];
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------
 // K2, persistent + software-pipelined form
 //   - workgroups walk the row blocks blockIdx.x, blockIdx.x + gridDim.x, ...; the reference-table
@@ -423,13 +324,12 @@ __global__ __launch_bounds__(NT, (NT == 384 ? 6 : 1)) void row_owner_jacobian_ke
 //     __syncthreads() (which implies vmcnt(0)) would stall on the stores in flight;
 //   - element records live in LDS (a scalar load per element inside the loop costs a memory round
 //     trip each: measured 1.6x slower).
-// DBG != 0 only in profiling launches (env MHA_K2_ABLATE): 1 no contributions, 2 no stores, 3 neither.
 // ---------------------------------------------------------------------------------------------
 constexpr int kMaxBlockElems = 27, kMaxBlockPairs = 256;  // caps of a row block (host: prepareRowOwner)
 
 
-template <int DIM, int N, int NT, typename SlotT, int DBG>
-__global__ __launch_bounds__(NT, (NT == 384 ? 5 : (NT == 256 ? 4 : 1))) void row_owner_jacobian_persistent_kernel(
+template <int DIM, int N, int NT, typename SlotT>
+__global__ __launch_bounds__(NT, 1) void row_owner_jacobian_persistent_kernel(
     RowBlocksDev rb, const double *__restrict__ erec, const double *__restrict__ khat,
     const uint4 *__restrict__ slot16, const uint16_t *__restrict__ pair_off16, const int *__restrict__ slot_pair,
     RowOut out, double su, double st) {
@@ -546,7 +446,7 @@ __global__ __launch_bounds__(NT, (NT == 384 ? 5 : (NT == 256 ? 4 : 1))) void row
     // v_readlane; the geometric factors are read with 16-byte accesses, only for elements the wave works on.
     const double mp_l = s_erec[min(lane, T - 1) * kERec + 7];
     const int mk_l = __double2loint(mp_l), pb_l = __double2hiint(mp_l);
-    for (int t = 0; t < ((DBG & 1) ? 0 : T); ++t) {
+    for (int t = 0; t < T; ++t) {
       const unsigned mask = (unsigned)__builtin_amdgcn_readlane(mk_l, t);
       if ((mask & wave_si) == 0u) continue;
       const int pb = __builtin_amdgcn_readlane(pb_l, t);
@@ -572,7 +472,7 @@ __global__ __launch_bounds__(NT, (NT == 384 ? 5 : (NT == 256 ? 4 : 1))) void row
     // stream the finished rows: each wave takes whole contiguous runs, reads four 512-byte pieces out of the
     // accumulator, issues their stores (left in flight) and zeroes what it has just read -- no other wave
     // touches these runs until the next block's accumulation, so one barrier per block suffices here
-    for (int j = 0; wave + NW * j < ((DBG & 2) ? 0 : NS); ++j) {
+    for (int j = 0; wave + NW * j < NS; ++j) {
       int len = __builtin_amdgcn_readlane(sg_len, j);
       const bool fixed_run = len < 0;  // run of fixed rows: zeros when storing, untouched when accumulating
       if (fixed_run) len = -len;
@@ -615,31 +515,13 @@ void launch_k2_t(RowBlocksDev rb, const AffineDev &af, const RowOut &out, double
   const size_t lds = k2_lds_bytes(rb, N, sizeof(SlotT));
   MHA_REQUIRE(lds <= 160 * 1024, MHA_ERR_INVALID, "row-owner kernel needs " << lds << " B of LDS (> 160 KiB)");
   MHA_REQUIRE(rb.lds_acc < 65536, MHA_ERR_INVALID, "row-owner kernel: accumulator offsets must fit 16 bits");
-  int mode = 1, per_cu = 3, dbg = 0;
-  if (const char *e = std::getenv("MHA_K2_MODE")) mode = std::atoi(e);            // tuning / profiling knobs
-  if (const char *e = std::getenv("MHA_K2_WGS_PER_CU")) per_cu = std::max(1, std::atoi(e));
-  if (const char *e = std::getenv("MHA_K2_ABLATE")) dbg = std::atoi(e);
-  if (mode == 1) {
-    MHA_REQUIRE(rb.lds_elems <= kMaxBlockElems && rb.lds_pairs <= kMaxBlockPairs && rb.lds_segs <= 64 * (NT / 64),
-                MHA_ERR_INVALID, "persistent row-owner kernel: row block exceeds its caps");
-    const size_t lds_p = lds + (size_t)rb.lds_elems * kERec * sizeof(double);
-    auto go = [&](auto kern) {
-      MHA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-      hipLaunchKernelGGL(kern, dim3(std::min(grid, 256 * per_cu)), dim3(NT), lds_p, stream, rb, af.erec, af.khat,
-                         static_cast<const uint4 *>(af.slot), af.pair_off16, af.slot_pair, out, su, st);
-    };
-    switch (dbg) {
-      case 1: go(row_owner_jacobian_persistent_kernel<DIM, N, NT, SlotT, 1>); break;
-      case 2: go(row_owner_jacobian_persistent_kernel<DIM, N, NT, SlotT, 2>); break;
-      case 3: go(row_owner_jacobian_persistent_kernel<DIM, N, NT, SlotT, 3>); break;
-      default: go(row_owner_jacobian_persistent_kernel<DIM, N, NT, SlotT, 0>); break;
-    }
-  } else {
-    auto kern = row_owner_jacobian_kernel<DIM, N, NT, SlotT>;
-    MHA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, stream, rb, af.erec, af.khat,
-                       static_cast<const uint4 *>(af.slot), af.pair_off16, out, su, st);
-  }
+  MHA_REQUIRE(rb.lds_elems <= kMaxBlockElems && rb.lds_pairs <= kMaxBlockPairs && rb.lds_segs <= 64 * (NT / 64),
+              MHA_ERR_INVALID, "persistent row-owner kernel: row block exceeds its caps");
+  const size_t lds_p = lds + (size_t)rb.lds_elems * kERec * sizeof(double);
+  auto kern = row_owner_jacobian_persistent_kernel<DIM, N, NT, SlotT>;
+  MHA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
+  hipLaunchKernelGGL(kern, dim3(std::min(grid, 256 * 3)), dim3(NT), lds_p, stream, rb, af.erec, af.khat,  // three workgroups per CU
+                     static_cast<const uint4 *>(af.slot), af.pair_off16, af.slot_pair, out, su, st);
   MHA_HIP(hipGetLastError());
 }
 
@@ -655,9 +537,7 @@ void launch_k1(const BlockDev &b, const ThermalDev &ph, const AffineDev &af, dou
   if (b.e_count <= 0) return;
   const bool tr = ph.time.transient != 0;
   const int grid = (b.e_count + kK1Elems - 1) / kK1Elems;
-  // MHA_K1_LDS_PAD: unused dynamic LDS per workgroup -- throttles how many K1 workgroups share a CU with K2 (experiment)
-  static const size_t pad = [] { const char *m = std::getenv("MHA_K1_LDS_PAD"); return m ? (size_t)std::atoi(m) : (size_t)0; }();
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kK1Threads), pad, stream, b, ph, af, res); };
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kK1Threads), 0, stream, b, ph, af, res); };
   if (has_expression(ph.source)) {  // the only named function K1 evaluates per point (coefficients are constants here)
     if (tr) go(thermal_affine_element_kernel<DIM, P, NQ1, true, true>);
     else go(thermal_affine_element_kernel<DIM, P, NQ1, false, true>);
@@ -730,12 +610,7 @@ void launch_row_owner_jacobian(int dim, int n, const RowBlocksDev &rb, const Aff
   if (dim == 2 && n == 9) return launch_k2<2, 9, 128>(rb, af, out, scale_u, scale_t, stream);
   if (dim == 2 && n == 25) return launch_k2<2, 25, 320>(rb, af, out, scale_u, scale_t, stream);
   if (dim == 3 && n == 8) return launch_k2<3, 8, 64>(rb, af, out, scale_u, scale_t, stream);
-  if (dim == 3 && n == 27) {
-    const char *e = std::getenv("MHA_K2_NT");  // tuning knob
-    if (e && std::atoi(e) == 384) return launch_k2<3, 27, 384>(rb, af, out, scale_u, scale_t, stream);
-    if (e && std::atoi(e) == 256) return launch_k2<3, 27, 256>(rb, af, out, scale_u, scale_t, stream);
-    return launch_k2<3, 27, 192>(rb, af, out, scale_u, scale_t, stream);
-  }
+  if (dim == 3 && n == 27) return launch_k2<3, 27, 192>(rb, af, out, scale_u, scale_t, stream);
   MHA_REQUIRE(false, MHA_ERR_INVALID, "row-owner Jacobian kernel: unsupported (dim, dofs/elem)");
 }
 
