@@ -467,6 +467,35 @@ def block_pattern_copy_plan(dim, nodes, lids, nrows, rowptr, colind, khat, facto
     return full, db, stores, dict(zip(("items", "segments", "max_item_segments", "span_entries", "segment_registers",
                                        "runs", "roles"), counts))
 
+def block_pattern_rep_plan(dim, nodes, lids, nrows, rowptr, colind, khat, factors, fixed=None, scale_u=1.0, scale_t=1.0,
+                           chunk_elems=16, num_cus=8, max_patterns=256):
+    """Host-only test hook: the geometry-database representatives' plan (one wavefront per unit column tile of every
+    role's first block), walked on the host as its kernel walks it; every W entry an item reads is checked against its
+    unit's class range (an error otherwise).  -> (vals_full: every row block assembled, vals_rep: NaN but for the
+    entries the items store, stores [nnz], expect [nnz]: 1 on the roles' first blocks, units [items][3]: role, part,
+    column tile, part_tiles [parts][2]: role, column tiles, dict)."""
+    lib = load_library()
+    nodes, lids, rowptr, colind = _np(nodes, np.float64), _np(lids, np.int32), _np(rowptr, np.int32), _np(colind, np.int32)
+    khat, factors = _np(khat, np.float64), _np(factors, np.float64)
+    fx = None if fixed is None else _np(fixed, np.uint8)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    nsym = khat.shape[0] - 1
+    nnz = len(colind)
+    full, rep = np.full(nnz, np.nan), np.full(nnz, np.nan)
+    stores, expect = np.zeros(nnz, np.int32), np.zeros(nnz, np.int8)
+    units, part_tiles = np.full((nnz // 16 + 4096, 3), -1, np.int32), np.full((nnz // 16 + 4096, 2), -1, np.int32)
+    counts = (C.c_int * 4)()
+    f = lib.mha_test_block_pattern_rep_plan
+    f.argtypes = ([C.c_int] * 6 + [C.c_void_p] * 7 + [C.c_double, C.c_double] + [C.c_int] * 3 + [C.c_void_p] * 5 +
+                  [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p])
+    _check(f(int(dim), int(nrows), lids.shape[0], nodes.shape[1], lids.shape[1], nsym, vp(nodes), vp(lids), vp(rowptr),
+             vp(colind), vp(fx), vp(khat), vp(factors), float(scale_u), float(scale_t), int(chunk_elems), int(num_cus),
+             int(max_patterns), vp(full), vp(rep), vp(stores), vp(expect), vp(units), units.size, vp(part_tiles),
+             part_tiles.size, counts))
+    info = dict(zip(("items", "roles", "parts", "runs"), counts))
+    return full, rep, stores, expect, units[:info["items"]], part_tiles[:info["parts"]], info
+
+
 def row_partition(dim, nodes, lids, nrows, rowptr, caps=None):
     """Host-only: the row-owner partition (mha_row_partition_*).  -> dict(row_ptr, rows, elem_ptr, elems, max_*)."""
     lib = load_library()

@@ -2150,29 +2150,20 @@ void AssemblyManager::prepareBlockPattern() {
   bp.usable = true;
   // Geometry-database mode (reference: identifyVolumetricDatabase, assemblyManager.cpp:4314-4467,
   // here with exact matching): with ONE geometry shape in the block the rows of a row block depend on its pattern
-  // only -- the kernel runs on one representative block per role (the role's first) and the representative's runs are
-  // replicated.  MHA_BP_DATABASE=0 keeps the full kernel.
+  // only -- the representatives (every unit of one block per role, the role's first; block_pattern_reps_kernel) are
+  // computed and their runs replicated.  MHA_BP_DATABASE=0 keeps the full kernel.
   bp.db_mode = false;
   const char *dbm = std::getenv("MHA_BP_DATABASE");
   if (ro_.num_shapes == 1 && !(dbm && dbm[0] == '0')) {
-    std::vector<int32_t> rseg(static_cast<size_t>(h.num_roles) * 4, 0), rptr(static_cast<size_t>(h.num_roles) + 1, 0);
-    for (int k = 0; k < h.num_roles; ++k) {
-      rseg[4 * k] = k;
-      rseg[4 * k + 1] = 0;
-      rseg[4 * k + 2] = 1;
-      rptr[k + 1] = k + 1;
-    }
+    const BpRepPlan rp = build_rep_plan(h);
     const CopyPlan cp = build_copy_plan(block_pattern_copy_runs(h), d.nnz);
-    bp.rep_seg.upload(rseg);
-    bp.rep_wg_seg_ptr.upload(rptr);
+    bp.rep_items.upload(rp.item);
+    bp.rep_lanes.upload(rp.lane);
+    bp.rep_num_items = rp.num_items();
     bp.copy_items.upload(cp.item);
     bp.copy_segs.upload(cp.seg);
     bp.copy_num_items = cp.num_items();
     bp.copy_num_segs = cp.num_segs();
-    bp.dev_rep = d;
-    bp.dev_rep.seg = bp.rep_seg.data();
-    bp.dev_rep.wg_seg_ptr = bp.rep_wg_seg_ptr.data();
-    bp.dev_rep.num_wgs = h.num_roles;
     bp.db_mode = true;
   }
 }
@@ -2383,7 +2374,8 @@ void AssemblyManager::launchRowOwner(bool compute_jacobian, bool overwrite, doub
   // K2: pattern GEMMs on the matrix cores when the rows group, row blocks otherwise
   if (bpat_.usable && bpat_.db_mode && out.overwrite && (reinterpret_cast<uintptr_t>(out.vals) & 127u) == 0) {  // (the copy's chunks sit on 128-byte lines of the caller's array)
     // geometry-database mode: the representatives' rows, then their copies (same stream: ordered)
-    launch_block_pattern_jacobian(bpat_.dev_rep, out, su, st, stream_);
+    launch_block_pattern_reps(bpat_.rep_items.data(), bpat_.rep_lanes.data(), bpat_.rep_num_items, bpat_.erec2.data(),
+                              bpat_.w.data(), out.vals, su, st, stream_);
     // (lines that mix copied and representative entries are stored whole: the representatives' lanes store back the
     // bits they read, which the kernel above wrote earlier on this stream; no other wavefront writes those lines)
     launch_line_copy(bpat_.copy_items.data(), bpat_.copy_num_items, bpat_.copy_segs.data(), bpat_.copy_num_segs, h_rowptr_[nrows_], out.vals, stream_);

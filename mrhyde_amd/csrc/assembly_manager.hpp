@@ -245,9 +245,9 @@ class AssemblyManager {
     DeviceBuffer<double> w, erec2;
     // geometry-database mode (one shape in the block): the kernel on one representative block per role + replication
     bool db_mode = false;
-    BlockPatternDev dev_rep;  // dev with the segment tables of the representatives
-    DeviceBuffer<int32_t> rep_seg, rep_wg_seg_ptr, copy_items, copy_segs;  // the copy plan: copy_plan.hpp
-    int copy_num_items = 0, copy_num_segs = 0;
+    DeviceBuffer<int32_t> rep_items, rep_lanes;  // the representatives, one wavefront per item (BpRepPlan)
+    DeviceBuffer<int32_t> copy_items, copy_segs;  // the copy plan: copy_plan.hpp
+    int rep_num_items = 0, copy_num_items = 0, copy_num_segs = 0;
   } bpat_;
   void prepareBlockPattern();
 

@@ -650,4 +650,81 @@ std::vector<CopyRun> block_pattern_copy_runs(const BlockPatternPlan &pl) {
   return runs;
 }
 
+BpRepPlan build_rep_plan(const BlockPatternPlan &pl) {
+  MHA_REQUIRE(pl.usable, MHA_ERR_STATE, "block patterns not usable: " << pl.why);
+  MHA_REQUIRE(pl.erec_elem.size() * kBpRecDoubles < (size_t(1) << 31) && pl.w.size() < (size_t(1) << 31), MHA_ERR_INVALID,
+              "representatives: element records or W images beyond 32-bit offsets");
+  BpRepPlan rp;
+  for (int k = 0; k < pl.num_roles; ++k) {
+    const int32_t *ro = &pl.role[static_cast<size_t>(k) * kBpRoleInts];
+    if (ro[R_NBLOCKS] < 1) continue;
+    const int64_t erec_base = (static_cast<int64_t>(ro[R_EREC_HI]) << 32) | static_cast<uint32_t>(ro[R_EREC_LO]);
+    const int64_t row_base = (static_cast<int64_t>(ro[R_ROWB_HI]) << 32) | static_cast<uint32_t>(ro[R_ROWB_LO]);
+    const int64_t woff = (static_cast<int64_t>(ro[R_WOFF_HI]) << 32) | static_cast<uint32_t>(ro[R_WOFF_LO]);
+    const int32_t *pp = &pl.part_ptr[static_cast<size_t>(k) * (kBpWaves + 1)];
+    for (int p = pp[0]; p < pp[kBpWaves]; ++p) {  // every unit of the role, whichever wavefront the full kernel gives it
+      const int32_t *h = &pl.part_hdr[static_cast<size_t>(p) * kBpHdrInts];
+      const int32_t *L = &pl.part_lane[static_cast<size_t>(p) * kBpLaneRows * 64];
+      const bool fixed_class = h[H_FLAGS] & 1;
+      const int ks = h[H_KS], len = h[H_LEN], stride = stride_for(h[H_NCT]);
+      MHA_REQUIRE(fixed_class || (ks >= 1 && ks <= kBpMaxKSteps), MHA_ERR_STATE, "representatives: a unit of products with " << ks << " k-steps");
+      for (int q = 0; q < h[H_NTILE] + ((h[H_FLAGS] & 2) ? 1 : 0); ++q) {
+        const int32_t it[kBpRepItemInts] = {fixed_class ? 0 : ks, 4 * stride, ro[R_WDOUBLES], fixed_class ? 1 : 0};
+        rp.item.insert(rp.item.end(), it, it + kBpRepItemInts);
+        rp.unit.insert(rp.unit.end(), {k, p, q});
+        const size_t base = rp.lane.size();
+        rp.lane.resize(base + static_cast<size_t>(kBpRepLaneRows) * 64, 0);
+        int32_t *R = rp.lane.data() + base;
+        for (int lane = 0; lane < 64; ++lane) {
+          const int col = 16 * (h[H_CT0] + q) + (lane & 15);  // plain column order: a column's products do not depend on it
+          for (int s = 0; s < kBpMaxKSteps; ++s) R[s * 64 + lane] = static_cast<int32_t>(erec_base * kBpRecDoubles + L[s * 64 + lane]);
+          for (int t = 0; t < 4; ++t) {
+            const int packed = L[(16 + t) * 64 + lane];
+            R[(16 + t) * 64 + lane] =
+                packed < 0 || col >= len ? -1 : pl.rowbase[static_cast<size_t>(row_base + (packed >> 20))] + (packed & 0xfffff) + col;
+          }
+          R[20 * 64 + lane] = static_cast<int32_t>(woff + h[H_WOFF] + static_cast<int64_t>(lane >> 4) * stride + col);
+        }
+      }
+    }
+  }
+  return rp;
+}
+
+void rep_plan_host_apply(const BlockPatternPlan &pl, const BpRepPlan &rp, const double *factors, double su, double st,
+                         double *vals, int32_t *stores) {
+  const int ke = pl.ke;
+  auto rec = [&](int32_t r) {  // erec2 entry r, as build_erec2_kernel lays the records out
+    const int e = pl.erec_elem[static_cast<size_t>(r / kBpRecDoubles)], m = r % kBpRecDoubles;
+    return e >= 0 && m < ke ? factors[static_cast<size_t>(e) * ke + m] : 0.0;
+  };
+  for (int i = 0; i < rp.num_items(); ++i) {
+    const int32_t *it = &rp.item[static_cast<size_t>(i) * kBpRepItemInts];
+    const int32_t *R = &rp.lane[static_cast<size_t>(i) * kBpRepLaneRows * 64];
+    const int role = rp.unit[3 * i], p = rp.unit[3 * i + 1];
+    const int32_t *ro = &pl.role[static_cast<size_t>(role) * kBpRoleInts];
+    const int32_t *h = &pl.part_hdr[static_cast<size_t>(p) * kBpHdrInts];
+    // the W range of the part's class (stiffness half): what every load of the item must stay inside
+    const int64_t wlo = ((static_cast<int64_t>(ro[R_WOFF_HI]) << 32) | static_cast<uint32_t>(ro[R_WOFF_LO])) + h[H_WOFF];
+    const int64_t whi = wlo + static_cast<int64_t>(h[H_KS]) * 4 * stride_for(h[H_NCT]);
+    MHA_REQUIRE(it[2] == ro[R_WDOUBLES] && whi + it[2] <= static_cast<int64_t>(pl.w.size()), MHA_ERR_STATE, "representatives: W halves misplaced");
+    for (int row = 0; row < 16; ++row)
+      for (int c = 0; c < 16; ++c) {
+        const int lane = ((row & 3) << 4) | c;  // D register t = row >> 2 of lane (row & 3) * 16 + c
+        const int dst = R[(16 + (row >> 2)) * 64 + lane];
+        if (dst < 0) continue;
+        double v = 0.0;
+        for (int s = 0; s < it[0]; ++s)
+          for (int kk = 0; kk < 4; ++kk) {
+            const int a_lane = kk * 16 + row, b_lane = kk * 16 + c;  // A[row = lane & 15][k = lane >> 4], B[k][col = lane & 15]
+            const int64_t wi = static_cast<int64_t>(R[20 * 64 + b_lane]) + static_cast<int64_t>(s) * it[1];
+            MHA_REQUIRE(wi >= wlo && wi < whi, MHA_ERR_STATE, "representatives: a W load outside the class of its unit");
+            v += rec(R[s * 64 + a_lane]) * (su * pl.w[static_cast<size_t>(wi)] + st * pl.w[static_cast<size_t>(wi + it[2])]);
+          }
+        vals[dst] = it[3] ? 0.0 : v;
+        if (stores) ++stores[dst];
+      }
+  }
+}
+
 }  // namespace mha

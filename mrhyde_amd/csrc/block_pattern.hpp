@@ -90,4 +90,23 @@ void block_patterns_host_apply(const BlockPatternPlan &plan, const double *facto
 // every role's first block and its runs of consecutive rows are copied to the same runs of the role's other blocks.
 std::vector<CopyRun> block_pattern_copy_runs(const BlockPatternPlan &plan);
 
+// The representatives of the geometry-database mode (kernels/block_pattern.hip, block_pattern_reps_kernel): every
+// (role, unit, column tile) of the roles' first blocks is one ITEM, one wavefront of its own.  A wavefront loads its
+// table row, then its A operands and its tile's W columns (both halves) at once, runs the tile's k-steps and stores its
+// rows: no LDS image, two dependent loads in all.  Every address is absolute, fixed for the mesh.
+constexpr int kBpRepItemInts = 4;   // per item: k-steps, doubles of W between k-steps, doubles from the stiffness to the mass half, 1 = fixed rows (zeros, no loads)
+constexpr int kBpRepLaneRows = 21;  // per item and lane: [0..15] erec2 entry of the A operand of k-step s, [16..19] CRS entry of result register t (-1: no store), [20] W entry of k-step 0
+struct BpRepPlan {
+  std::vector<int32_t> item;  // [num_items][kBpRepItemInts]
+  std::vector<int32_t> lane;  // [num_items][kBpRepLaneRows][64]
+  std::vector<int32_t> unit;  // [num_items][3]: role, part, column tile (not read by the kernel)
+  int num_items() const { return static_cast<int>(item.size() / kBpRepItemInts); }
+};
+BpRepPlan build_rep_plan(const BlockPatternPlan &plan);
+
+// The kernel's arithmetic on the host, item by item (products in k-step order; factors: [E][ke]).  Every W entry an
+// item reads is checked against the W range of its part's class; stores: optional counters [nnz], one per entry stored.
+void rep_plan_host_apply(const BlockPatternPlan &plan, const BpRepPlan &rep, const double *factors, double su, double st,
+                         double *vals, int32_t *stores);
+
 }  // namespace mha

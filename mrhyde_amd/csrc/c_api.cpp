@@ -744,6 +744,47 @@ int mha_test_block_pattern_copy_plan(int dim, int num_rows, int num_elems, int n
   });
 }
 
+// The geometry-database representatives' plan (BpRepPlan) on the host.  vals_full: every row block assembled;
+// vals_rep: the representatives' items walked as the kernel walks them (NaN elsewhere, as the caller filled it);
+// stores: entries stored per position; expect: 1 on the entries of every role's first block.  units: [items][3] role,
+// part, column tile; part_tiles: [parts][2] role, column tiles of the part.
+int mha_test_block_pattern_rep_plan(int dim, int num_rows, int num_elems, int nnodes, int n, int nsym,
+                                    const double *nodes, const int32_t *lids, const int32_t *rowptr,
+                                    const int32_t *colind, const uint8_t *fixed, const double *khat,
+                                    const double *factors, double scale_u, double scale_t, int chunk_elems, int num_cus,
+                                    int max_patterns, double *vals_full, double *vals_rep, int32_t *stores, int8_t *expect,
+                                    int32_t *units, int64_t units_len, int32_t *part_tiles, int64_t part_tiles_len,
+                                    int *counts) {
+  return guarded([&] {
+    MHA_REQUIRE(factors && vals_full && vals_rep && stores && expect && units && part_tiles && counts, MHA_ERR_INVALID, "null argument");
+    const mha::BlockPatternPlan pl = test_block_patterns(dim, num_rows, num_elems, nnodes, n, nsym, nodes, lids, rowptr,
+                                                         colind, fixed, khat, chunk_elems, num_cus, max_patterns);
+    const mha::BpRepPlan rp = mha::build_rep_plan(pl);
+    MHA_REQUIRE(units_len >= 3ll * rp.num_items() && part_tiles_len >= 2ll * pl.num_parts, MHA_ERR_INVALID, "output arrays too short");
+    mha::block_patterns_host_apply(pl, factors, scale_u, scale_t, true, vals_full);
+    mha::rep_plan_host_apply(pl, rp, factors, scale_u, scale_t, vals_rep, stores);
+    const std::vector<mha::CopyRun> runs = mha::block_pattern_copy_runs(pl);
+    for (int k = 0; k < pl.num_roles; ++k) {  // the roles' first blocks: their runs of rows (the copy's sources)
+      const int32_t *ro = &pl.role[static_cast<size_t>(k) * mha::kBpRoleInts];
+      const int64_t row_base = (static_cast<int64_t>(ro[4]) << 32) | static_cast<uint32_t>(ro[3]);
+      const int32_t *rl = &pl.runlen[static_cast<size_t>(pl.role_runlen_off[k])];
+      for (int r = 0; r < ro[5]; ++r)
+        for (int e = 0; e < rl[r]; ++e) expect[pl.rowbase[static_cast<size_t>(row_base + r)] + e] = 1;
+    }
+    std::copy(rp.unit.begin(), rp.unit.end(), units);
+    for (int k = 0; k < pl.num_roles; ++k)
+      for (int p = pl.part_ptr[static_cast<size_t>(k) * (mha::kBpWaves + 1)]; p < pl.part_ptr[static_cast<size_t>(k) * (mha::kBpWaves + 1) + mha::kBpWaves]; ++p) {
+        const int32_t *h = &pl.part_hdr[static_cast<size_t>(p) * mha::kBpHdrInts];
+        part_tiles[2 * p] = k;
+        part_tiles[2 * p + 1] = h[5] + ((h[6] & 2) ? 1 : 0);  // H_NTILE, H_FLAGS bit 2: the tail tile
+      }
+    counts[0] = rp.num_items();
+    counts[1] = pl.num_roles;
+    counts[2] = pl.num_parts;
+    counts[3] = static_cast<int>(runs.size());
+  });
+}
+
 int mha_export_plan_create(int num_neighbors, const int32_t *neighbor_ranks, const int64_t *send_val_ptr,
                            const int32_t *send_val_index, const int64_t *send_row_ptr, const int32_t *send_row_index,
                            const int64_t *recv_val_ptr, const int32_t *recv_val_target, const int64_t *recv_row_ptr,

@@ -96,6 +96,11 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
+// An entry of W as the products read it: the stiffness half times su plus the mass half times st.  The full kernel's LDS
+// image and the representatives' registers both go through here, spelt as the one product and one fma the image has
+// always been compiled to, so that both paths round every entry alike.
+__device__ __forceinline__ double bp_w_entry(double su, double k, double st, double m) { return __builtin_fma(su, k, st * m); }
+
 struct UnitCtx {
   v4i erec;                // role's element records (buffer resource)
   v4i out;                 // the CRS values (buffer resource)
@@ -433,7 +438,7 @@ __global__ __launch_bounds__(kBpWaves * 64) void block_pattern_jacobian_kernel(B
       const int n2 = ro[R_WDOUBLES] / 2;
       for (int i = tid; i < n2; i += kBpWaves * 64) {
         const double2 a = srck[i], b = srcm[i];
-        dst[i] = make_double2(su * a.x + st * b.x, su * a.y + st * b.y);
+        dst[i] = make_double2(bp_w_entry(su, a.x, st, b.x), bp_w_entry(su, a.y, st, b.y));
       }
     }
     c.first = __builtin_amdgcn_readfirstlane(d.seg[4 * sg + 1]);
@@ -545,7 +550,76 @@ __global__ __launch_bounds__(kBpWaves * 64) void block_pattern_jacobian_kernel(B
   }
 }
 
+// The representatives of the geometry-database mode: one wavefront per item (block_pattern.hpp, BpRepPlan) -- one 16-column
+// tile of one unit of a role's first block.  The item's table row is loaded first; then its A operands and both halves
+// of its W columns, exactly KS of each, are all in flight before the first wait; the k-steps run in order on the same
+// MFMA as the full kernel, the W entries combined by the same helper (the full kernel skips only products of all-zero W
+// blocks, which add exactly +0 to an accumulator that is never -0).  Plain column order: an entry's products do not
+// depend on which other columns share the instruction.  Fixed rows: zeros, no loads.
+template <int KS>
+__device__ __forceinline__ void rep_item(const int32_t *__restrict__ L, int wstep, int whalf, const int (&dst)[4],
+                                         const double *__restrict__ erec2, const double *__restrict__ w,
+                                         double *__restrict__ vals, double su, double st) {
+  unsigned ao[KS];
+#pragma unroll
+  for (int s = 0; s < KS; ++s) ao[s] = (unsigned)L[s * 64];
+  const unsigned w0 = (unsigned)L[20 * 64];
+  __builtin_amdgcn_sched_barrier(0);  // (without the fences hipcc interleaves the loads with the products: a third latency)
+  double a[KS], wk[KS], wm[KS];
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    const unsigned wi = w0 + (unsigned)(s * wstep);
+    wk[s] = w[wi];
+    wm[s] = w[wi + (unsigned)whalf];
+    a[s] = erec2[ao[s]];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  v4d acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int s = 0; s < KS; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], bp_w_entry(su, wk[s], st, wm[s]), acc, 0, 0, 0);
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+    if (dst[t] >= 0) vals[dst[t]] = acc[t];
+}
+
+__global__ __launch_bounds__(256) void block_pattern_reps_kernel(const int32_t *__restrict__ items, const int32_t *__restrict__ lanes,
+                                                                 int nitems, const double *__restrict__ erec2,
+                                                                 const double *__restrict__ w, double *__restrict__ vals,
+                                                                 double su, double st) {
+  const int lane = threadIdx.x & 63;
+  const int it = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (it >= nitems) return;
+  const int32_t *hd = items + (size_t)it * kBpRepItemInts;
+  const int ks = hd[0], wstep = hd[1], whalf = hd[2], fixed_rows = hd[3];
+  const int32_t *L = lanes + (size_t)it * kBpRepLaneRows * 64 + lane;
+  int dst[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) dst[t] = L[(16 + t) * 64];
+  if (fixed_rows) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      if (dst[t] >= 0) vals[dst[t]] = 0.0;
+    return;
+  }
+  switch (ks) {  // wave-uniform; the host plan has 1 <= ks <= kBpMaxKSteps for every item of products
+#define BP_REP(K_) case K_: rep_item<K_>(L, wstep, whalf, dst, erec2, w, vals, su, st); break;
+    BP_REP(1) BP_REP(2) BP_REP(3) BP_REP(4) BP_REP(5) BP_REP(6) BP_REP(7) BP_REP(8)
+    BP_REP(9) BP_REP(10) BP_REP(11) BP_REP(12) BP_REP(13) BP_REP(14) BP_REP(15) BP_REP(16)
+#undef BP_REP
+    default: break;
+  }
+  static_assert(kBpMaxKSteps == 16, "one instantiation per depth");
+}
+
 }  // namespace
+
+void launch_block_pattern_reps(const int32_t *items, const int32_t *lanes, int nitems, const double *erec2, const double *w,
+                               double *vals, double su, double st, hipStream_t stream) {
+  if (nitems <= 0 || !vals) return;
+  hipLaunchKernelGGL(block_pattern_reps_kernel, dim3((nitems + 3) / 4), dim3(256), 0, stream, items, lanes, nitems, erec2, w,
+                     vals, su, st);
+  MHA_HIP(hipGetLastError());
+}
 
 void launch_build_erec2(int64_t total_records, int nsym, const int32_t *erec_elem, const double *geo, double *erec2,
                         hipStream_t stream) {

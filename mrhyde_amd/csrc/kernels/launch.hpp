@@ -78,6 +78,9 @@ void launch_affine_geometry(const BlockDev &b, double *geo, hipStream_t stream);
 void launch_build_erec2(int64_t total_records, int nsym, const int32_t *erec_elem, const double *geo, double *erec2,
                         hipStream_t stream);
 void launch_block_pattern_jacobian(const BlockPatternDev &d, const RowOut &out, double su, double st, hipStream_t stream);
+// the geometry-database mode's representatives, one wavefront per item of the BpRepPlan (block_pattern.hpp)
+void launch_block_pattern_reps(const int32_t *items, const int32_t *lanes, int nitems, const double *erec2, const double *w,
+                               double *vals, double su, double st, hipStream_t stream);
 // line_copy.hip: the database modes' copy of representative entries inside vals in whole 128-byte lines
 // (copy_plan.hpp: items [n][4], segments [nseg][2]); vals must start on a 128-byte line
 void launch_line_copy(const int32_t *items, int nitems, const int32_t *seg, int nseg, int64_t nnz, double *vals,

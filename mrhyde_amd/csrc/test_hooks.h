@@ -39,6 +39,20 @@ int mha_test_block_pattern_copy_plan(int dim, int num_rows, int num_elems, int n
                                      double *vals_full, double *vals_db, int32_t *stores, int64_t stores_len,
                                      int *counts);
 
+/* The geometry-database representatives' plan on the host (block_pattern.hpp, BpRepPlan): vals_full = every row block
+ * assembled (as mha_test_block_patterns_host_apply); vals_rep (caller-filled) gets what the items store, walked with the
+ * kernel's arithmetic; every W entry an item reads is checked against the class range of its unit (an error otherwise).
+ * stores [nnz]: incremented per stored entry; expect [nnz]: set to 1 on the entries of the roles' first blocks.
+ * units [units_len >= 3 x items]: role, part, column tile of every item; part_tiles [>= 2 x parts]: role, column tiles.
+ * counts[4] = {items, roles, parts, copy runs}. */
+int mha_test_block_pattern_rep_plan(int dim, int num_rows, int num_elems, int nnodes, int n, int nsym,
+                                    const double *nodes, const int32_t *lids, const int32_t *rowptr,
+                                    const int32_t *colind, const uint8_t *fixed, const double *khat,
+                                    const double *factors, double scale_u, double scale_t, int chunk_elems, int num_cus,
+                                    int max_patterns, double *vals_full, double *vals_rep, int32_t *stores, int8_t *expect,
+                                    int32_t *units, int64_t units_len, int32_t *part_tiles, int64_t part_tiles_len,
+                                    int *counts);
+
 #ifdef __cplusplus
 }
 #endif
