@@ -417,7 +417,45 @@ int mha_boundary_view(mha_context *ctx, int group_id, const char *name, void **d
  * (navierstokes.cpp:45-46) and "fix_uz_offsets": the reference scatters the 3-D uz momentum
  * block through uy's offsets (navierstokes.cpp:688); 0 (default) reproduces that, 1 uses uz's;
  * shallowwaterHybridized: "g" (shallowwaterHybridized.cpp:72, default 9.81).                     */
+/* porousMixed (porousMixed.cpp:46-120) also takes: "use permeability data" (Kinv_xx = Kinv_yy = Kinv_zz = 1 / data(elem, 0)
+ * from the block's element data, in place of the Kinv_* functions, updatePerm :550-563; total_mobility still divides);
+ * "use KL expansion" (Kinv_dd divided by exp(KL_dd), a Karhunen-Loeve field evaluated at every integration point,
+ * updateKLPerm :567-714) with the "KL parameters" sublist flattened to "KL N x", "KL L x", "KL sigma x", "KL eta x" and
+ * the same for y and z (2-D: x and y); N is at most MHA_KL_MAX_TERMS per direction.  "fix_KL_3d" (default 0) reproduces
+ * the 3-D KLUQcoeffs branch of the reference (lambda_z from the y expansion, the term twice into KL_xx, once into
+ * KL_yy, never into KL_zz, :614-637); 1 uses lambda_z and adds every term once to each component.  Either option makes
+ * the porousMixed database mode decline (mha_get_info "porous_direct" then reads 1).  Heterogeneous permeability with
+ * deck-string functions is refused. */
 int mha_set_physics_parameter(mha_context *ctx, const char *name, double value);
+
+/* ---- porousMixed heterogeneous permeability -----------------------------------------------
+ * Element data of the block, [num_elems][ncols] host array in mha_set_mesh element order, copied and owned by the
+ * context (the analogue of groups[block][grp]->data; column 0 is the permeability).  ncols >= 1; data(e, 0) must be
+ * finite and nonzero.  A new mesh drops it.  "use permeability data" without element data fails at assembly time with
+ * MHA_ERR_STATE.  Waits for the context's stream before replacing an earlier array. */
+#define MHA_KL_MAX_TERMS 8
+int mha_set_element_data(mha_context *ctx, int ncols, const double *data_host);
+/* AssemblyManager::importMeshData (assemblyManager.cpp:8235-8400), non-grid branch: each element takes the value row of
+ * the data point nearest to its centre (the reference-cell centre in the physical frame: the vertex average of a Q1
+ * cell), squared Euclidean distance, ties to the lowest point index (tools/data.cpp:391-420); then as
+ * mha_set_element_data.  points_host [npts][dim], values_host [npts][ncols]; seed_out (nullable) [num_elems] receives
+ * the chosen point of every element (data_seed). */
+int mha_import_mesh_data(mha_context *ctx, int64_t npts, const double *points_host, int ncols, const double *values_host,
+                         int32_t *seed_out);
+/* A vector-valued parameter of the physics module (wkset->getParameter); porousMixed: "KLUQcoeffs" (terms
+ * 0 .. min(n, nterms)) and "KLStochcoeffs" (terms prog .. min(nterms, prog + n), prog = the length of KLUQcoeffs if that
+ * is set, 0 otherwise).  Any other name is refused.  The values are copied; they take effect at the next assembly, which
+ * waits for the work already queued on the context's stream before it replaces the device tables.  Between UQ samples
+ * this is the only call needed. */
+int mha_set_parameter_vector(mha_context *ctx, const char *name, int n, const double *values_host);
+/* Host-only, no GPU needed.  mha_closest_points: for each of nq query points [nq][dim] the index of the nearest of np
+ * points [np][dim] (exact; as mha_import_mesh_data).  mha_kl_expansion: the first N roots omega and eigenvalues lambda
+ * of one 1-D expansion (tools/klexpansion.hpp:38-90; N <= MHA_KL_MAX_TERMS; fewer than N roots found is an error).
+ * mha_kl_indices: the multi-indices [prod N][dim] of a 2-D or 3-D expansion in the reference's total order
+ * (porousMixed.cpp:73-118). */
+int mha_closest_points(int dim, int64_t nq, const double *query, int64_t np, const double *points, int32_t *idx_out);
+int mha_kl_expansion(int N, double L, double sigma, double eta, double *omega_out, double *lambda_out);
+int mha_kl_indices(int dim, const int N[3], int32_t *idx_out);
 
 /* ---- shallowwaterHybridized side terms ---------------------------------------------------
  * replaces: computeFluxVector(on_side) :409-480, eigendecompFluxJacobian :765-823,

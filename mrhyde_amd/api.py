@@ -29,7 +29,10 @@ EXPORTS = [
     "mha_workset_compute_solution", "mha_workset_compute_residual",
     "mha_sparse3d_create", "mha_sparse3d_views", "mha_sparse3d_size", "mha_sparse3d_destroy", "mha_database_build",
     "mha_database_get", "mha_apply_mass_matrix_free", "mha_swhdg_subgrid_workspace_bytes", "mha_swhdg_subgrid_solve",
+    "mha_set_element_data", "mha_import_mesh_data", "mha_set_parameter_vector", "mha_closest_points", "mha_kl_expansion",
+    "mha_kl_indices",
 ]
+KL_MAX_TERMS = 8  # MHA_KL_MAX_TERMS: KL roots per direction the kernels evaluate
 MASS_ON_THE_FLY, MASS_LOCAL, MASS_DATABASE, MASS_DATABASE_SPARSE = 0, 1, 2, 3
 SWH_INTERFACE, SWH_FARFIELD, SWH_SLIP = 0, 1, 2
 BASIS_HGRAD, BASIS_HVOL, BASIS_HDIV = 0, 1, 2
@@ -128,6 +131,12 @@ def load_library():
         _lib.mha_batched_condense.argtypes = [C.c_int, C.c_int, C.c_int64] + [C.c_void_p] * 7
         _lib.mha_swhdg_side_terms.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int64] + [C.c_void_p] * 10
         _lib.mha_swhdg_eigendecomp.argtypes = [C.c_double, C.c_int64] + [C.c_void_p] * 6
+        _lib.mha_set_element_data.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _lib.mha_import_mesh_data.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.mha_set_parameter_vector.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p]
+        _lib.mha_closest_points.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        _lib.mha_kl_expansion.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        _lib.mha_kl_indices.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -362,6 +371,34 @@ def swhdg_eigendecomp(g, Shat, normals):
     R = torch.zeros_like(L)
     _check(load_library().mha_swhdg_eigendecomp(float(g), npts, _ptr(Shat), _ptr(normals), _ptr(L), _ptr(lam), _ptr(R), None))
     return L, lam, R
+
+
+def closest_points(query, points):
+    """Index of the nearest of points [np, dim] for every row of query [nq, dim] (squared Euclidean distance, ties to the
+    lowest index; mha_closest_points, host only).  -> int32 [nq]."""
+    q, p = np.atleast_2d(_np(query, np.float64)), np.atleast_2d(_np(points, np.float64))
+    assert q.shape[1] == p.shape[1], "query and points differ in dimension"
+    idx = np.zeros(q.shape[0], dtype=np.int32)
+    _check(load_library().mha_closest_points(q.shape[1], q.shape[0], q.ctypes.data_as(C.c_void_p), p.shape[0],
+                                             p.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p)))
+    return idx
+
+
+def kl_expansion(N, L, sigma, eta):
+    """The first N roots omega and eigenvalues lambda of a 1-D KL expansion (mha_kl_expansion, host only)."""
+    om, lam = np.zeros(N), np.zeros(N)
+    _check(load_library().mha_kl_expansion(int(N), float(L), float(sigma), float(eta), om.ctypes.data_as(C.c_void_p),
+                                           lam.ctypes.data_as(C.c_void_p)))
+    return om, lam
+
+
+def kl_indices(dim, N):
+    """Multi-indices [prod N, dim] of a dim-D KL expansion in the reference's total order (mha_kl_indices, host only)."""
+    n = np.ones(3, dtype=np.int32)
+    n[:len(N)] = N
+    idx = np.zeros((int(np.prod(n[:dim])), dim), dtype=np.int32)
+    _check(load_library().mha_kl_indices(int(dim), n.ctypes.data_as(C.c_void_p), idx.ctypes.data_as(C.c_void_p)))
+    return idx
 
 
 def mesh_structured(dim, order, ncell, lo=None, hi=None):
@@ -779,6 +816,28 @@ class Block:
 
     def set_physics_parameter(self, name, value):
         _check(load_library().mha_set_physics_parameter(self._h, name.encode(), float(value)))
+
+    # -- porousMixed heterogeneous permeability -----------------------------------
+    def set_element_data(self, data):
+        """Element data [E, ncols] (host array, set_mesh element order; column 0 is the permeability)."""
+        d = _np(data, np.float64)
+        d = d.reshape(d.shape[0], -1)
+        _check(load_library().mha_set_element_data(self._h, d.shape[1], d.ctypes.data_as(C.c_void_p)))
+
+    def import_mesh_data(self, points, values):
+        """Each element takes the values row of the data point nearest to its centre.  points [np, dim], values
+        [np, ncols] (host arrays).  -> the chosen point of every element (int32 [E])."""
+        p, v = _np(points, np.float64), _np(values, np.float64)
+        v = v.reshape(p.shape[0], -1)
+        seed = np.zeros(self.info("num_elems"), dtype=np.int32)
+        _check(load_library().mha_import_mesh_data(self._h, p.shape[0], p.ctypes.data_as(C.c_void_p), v.shape[1],
+                                                   v.ctypes.data_as(C.c_void_p), seed.ctypes.data_as(C.c_void_p)))
+        return seed
+
+    def set_parameter_vector(self, name, values):
+        """"KLUQcoeffs" / "KLStochcoeffs" (host array); takes effect at the next assembly."""
+        v = _np(values, np.float64).ravel()
+        _check(load_library().mha_set_parameter_vector(self._h, name.encode(), len(v), v.ctypes.data_as(C.c_void_p)))
 
     # -- workset views ---------------------------------------------------------
     def num_worksets(self):

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "mesh.hpp"
+#include "porous_data.hpp"
 
 namespace mha {
 
@@ -98,6 +99,9 @@ AssemblyManager::~AssemblyManager() {
 void AssemblyManager::setMesh(int nelem, const double *nodes, const int32_t *lids, const int32_t *offsets,
                               int nrows, const uint8_t *fixed) {
   boundary_groups_.clear();  // entries refer to the previous mesh's element ids
+  d_elem_data_.resize(0);    // so does the element data
+  wkset_.elem_data = nullptr;
+  wkset_.elem_data_cols = 0;
   has_orient_ = false;
   d_orient_.resize(0);
   MHA_REQUIRE(nelem > 0 && nrows > 0 && nodes && lids && offsets, MHA_ERR_INVALID, "mha_set_mesh: null or empty input");
@@ -839,6 +843,8 @@ void AssemblyManager::assemblePorousDirect(ElemOut o, int compute_jacobian, bool
   bool pdb = overwrite && compute_jacobian && (reinterpret_cast<uintptr_t>(crs_vals) & 127u) == 0;
   for (const char *name : {"Kinv_xx", "Kinv_yy", "Kinv_zz", "total_mobility"})
     pdb = pdb && functions_.has(name) && functions_.evaluate(name).kind == MHA_FUNC_CONSTANT;
+  // heterogeneous permeability: every element has its own matrix, which the geometry database cannot see
+  if (pdb && physics_->heterogeneous()) { porous_db_.why = "heterogeneous permeability (element data or KL field)"; pdb = false; }
   pdb = pdb && porousDatabaseUsable();
   if (pdb && functions_.evaluate("source").kind != MHA_FUNC_EXPRESSION) {
     // database mode: the lean build (residual parts only) over all elements, then the full build over the few
@@ -1752,6 +1758,52 @@ View AssemblyManager::boundaryView(int group, const std::string &name) const {
 void AssemblyManager::setPhysicsParameter(const std::string &name, double value) {
   MHA_REQUIRE(physics_ != nullptr, MHA_ERR_STATE, "no physics module: call mha_physics_select first");
   physics_->setParameter(name, value);
+}
+
+// reference: wkset->getParameter (the parameter manager's vectors); a new vector takes effect at the next assembly
+void AssemblyManager::setParameterVector(const std::string &name, int n, const double *values) {
+  MHA_REQUIRE(physics_ != nullptr, MHA_ERR_STATE, "no physics module: call mha_physics_select first");
+  physics_->setParameterVector(name, values, n);
+}
+
+void AssemblyManager::setElementData(int ncols, const double *data) {
+  MHA_REQUIRE(has_mesh_, MHA_ERR_STATE, "element data before mha_set_mesh");
+  MHA_REQUIRE(ncols >= 1, MHA_ERR_INVALID, "element data: ncols must be at least 1");
+  MHA_REQUIRE(data != nullptr, MHA_ERR_INVALID, "element data: null array");
+  for (int e = 0; e < nelem_; ++e) {
+    const double v = data[static_cast<size_t>(e) * ncols];
+    // (column 0 is a permeability: Kinv = 1 / data(elem, 0) would put inf or NaN into the matrix)
+    MHA_REQUIRE(std::isfinite(v) && v != 0.0, MHA_ERR_INVALID, "element data: data(" << e << ", 0) = " << v << " is zero or not finite");
+  }
+  // an assembly queued earlier on the stream may still read the old array
+  MHA_HIP(hipStreamSynchronize(stream_));
+  d_elem_data_.upload(data, static_cast<size_t>(nelem_) * ncols);
+  wkset_.elem_data = d_elem_data_.data();
+  wkset_.elem_data_cols = ncols;
+}
+
+// non-grid branch: the element centre is the reference-cell centre mapped to the physical frame (meshInterface.cpp:643-660),
+// for the Q1 geometry of the block the vertex average
+void AssemblyManager::importMeshData(int64_t npts, const double *points, int ncols, const double *values, int32_t *seed) {
+  MHA_REQUIRE(has_mesh_, MHA_ERR_STATE, "mesh data before mha_set_mesh");
+  MHA_REQUIRE(ncols >= 1, MHA_ERR_INVALID, "mesh data: ncols must be at least 1");
+  MHA_REQUIRE(npts >= 1 && points && values, MHA_ERR_INVALID, "mesh data: no data points");
+  std::vector<double> nodes(static_cast<size_t>(nelem_) * nnodes_ * dim_), centres(static_cast<size_t>(nelem_) * dim_);
+  d_nodes_.download(nodes.data());
+  const double wv = 1.0 / nnodes_;
+  for (int e = 0; e < nelem_; ++e)
+    for (int d = 0; d < dim_; ++d) {
+      double s = 0.0;
+      for (int k = 0; k < nnodes_; ++k) s += nodes[(static_cast<size_t>(e) * nnodes_ + k) * dim_ + d];
+      centres[static_cast<size_t>(e) * dim_ + d] = s * wv;
+    }
+  std::vector<int32_t> near(nelem_);
+  closest_points(dim_, nelem_, centres.data(), npts, points, near.data());
+  std::vector<double> data(static_cast<size_t>(nelem_) * ncols);
+  for (int e = 0; e < nelem_; ++e)
+    for (int c = 0; c < ncols; ++c) data[static_cast<size_t>(e) * ncols + c] = values[static_cast<size_t>(near[e]) * ncols + c];
+  setElementData(ncols, data.data());
+  if (seed) std::copy(near.begin(), near.end(), seed);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -84,6 +84,11 @@ class AssemblyManager {
   void boundaryUpdate(int group);
   View boundaryView(int group, const std::string &name) const;
   void setPhysicsParameter(const std::string &name, double value);
+  void setParameterVector(const std::string &name, int n, const double *values);
+  // the block's element data [E][ncols] (reference: groups->data); importMeshData picks each element's row as the data
+  // point nearest to its centre (AssemblyManager::importMeshData, assemblyManager.cpp:8235-8400)
+  void setElementData(int ncols, const double *data);
+  void importMeshData(int64_t npts, const double *points, int ncols, const double *values, int32_t *seed);
   void applyDbcDiag(double *crs_vals);
   void gather(const double *vec, double *elem_vals);
 
@@ -181,6 +186,7 @@ class AssemblyManager {
   void prepareElemSlots();
   void useGeneralKernel(bool need_slots);
   DeviceBuffer<double> d_nodes_;
+  DeviceBuffer<double> d_elem_data_;  // setElementData
   DeviceBuffer<int32_t> d_lids_, d_offsets_, d_rowptr_, d_colind_;
   DeviceBuffer<uint8_t> d_fixed_;
   std::vector<int32_t> h_lids_, h_rowptr_, h_colind_;

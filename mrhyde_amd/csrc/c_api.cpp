@@ -1,5 +1,6 @@
 // c_api.cpp -- extern "C" boundary (include/mrhyde_amd.h) over the C++ host layer.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -10,6 +11,7 @@
 #include "row_blocks.hpp"
 #include "block_pattern.hpp"
 #include "newton.hpp"
+#include "porous_data.hpp"
 #include "test_hooks.h"
 #include "scatter_plan.hpp"
 #include "export_plan.hpp"
@@ -411,6 +413,56 @@ int mha_set_physics_parameter(mha_context *ctx, const char *name, double value) 
   return guarded([&] {
     MHA_REQUIRE(name, MHA_ERR_INVALID, "null argument");
     mgr(ctx).setPhysicsParameter(name, value);
+  });
+}
+
+// reference: groups[block][grp]->data (set by AssemblyManager::importMeshData, assemblyManager.cpp:8235-8400)
+int mha_set_element_data(mha_context *ctx, int ncols, const double *data_host) {
+  return guarded([&] { mgr(ctx).setElementData(ncols, data_host); });
+}
+
+// reference: AssemblyManager::importMeshData (assemblyManager.cpp:8235-8400), non-grid branch
+int mha_import_mesh_data(mha_context *ctx, int64_t npts, const double *points_host, int ncols, const double *values_host,
+                         int32_t *seed_out) {
+  return guarded([&] { mgr(ctx).importMeshData(npts, points_host, ncols, values_host, seed_out); });
+}
+
+// reference: wkset->getParameter("KLUQcoeffs" / "KLStochcoeffs") in porousMixed::updateKLPerm (porousMixed.cpp:573, 642)
+int mha_set_parameter_vector(mha_context *ctx, const char *name, int n, const double *values_host) {
+  return guarded([&] {
+    MHA_REQUIRE(name, MHA_ERR_INVALID, "null argument");
+    mgr(ctx).setParameterVector(name, n, values_host);
+  });
+}
+
+// reference: Data::findClosestPoint (tools/data.cpp:391-420)
+int mha_closest_points(int dim, int64_t nq, const double *query, int64_t np, const double *points, int32_t *idx_out) {
+  return guarded([&] { mha::closest_points(dim, nq, query, np, points, idx_out); });
+}
+
+// reference: klexpansion::computeRoots / getEval (tools/klexpansion.hpp:38-125)
+int mha_kl_expansion(int N, double L, double sigma, double eta, double *omega_out, double *lambda_out) {
+  return guarded([&] {
+    MHA_REQUIRE(N >= 1 && N <= MHA_KL_MAX_TERMS, MHA_ERR_INVALID, "KL expansion: N must be in 1.." << MHA_KL_MAX_TERMS);
+    MHA_REQUIRE(std::isfinite(L) && L > 0.0 && std::isfinite(eta) && eta > 0.0 && std::isfinite(sigma), MHA_ERR_INVALID,
+                "KL expansion: L and eta must be positive, sigma finite");
+    double om[MHA_KL_MAX_TERMS], lam[MHA_KL_MAX_TERMS];
+    const int found = mha::kl_roots(N, L, sigma, eta, om, lam);
+    MHA_REQUIRE(found == N, MHA_ERR_INVALID, "KL expansion: found " << found << " of " << N << " roots");
+    for (int k = 0; k < N; ++k) {
+      if (omega_out) omega_out[k] = om[k];
+      if (lambda_out) lambda_out[k] = lam[k];
+    }
+  });
+}
+
+// reference: the KLindices of the porousMixed constructor (porousMixed.cpp:73-118)
+int mha_kl_indices(int dim, const int N[3], int32_t *idx_out) {
+  return guarded([&] {
+    MHA_REQUIRE(N && idx_out, MHA_ERR_INVALID, "null argument");
+    std::vector<int32_t> idx;
+    mha::kl_indices(dim, N, idx);
+    std::copy(idx.begin(), idx.end(), idx_out);
   });
 }
 

@@ -218,6 +218,47 @@ __device__ __forceinline__ double eval_func(const FuncDesc &f, int e, int q, int
   return s;
 }
 
+// porousMixed KL log-fields KL_dd at the physical point x (PorousHetDev; reference: updateKLPerm, porousMixed.cpp:567-714):
+//   KL_c = sum_{k,j,i} C[k][j][i][c] phi_x,i(x) phi_y,j(y) phi_z,k(z).
+// The x and y eigenfunctions are kept in registers, filled and read by unrolled loops (static indices); z runs in a
+// runtime loop.  Table and coefficients are read at wave-uniform addresses.  sum_d N_d sin/cos pairs per point.
+template <int DIM>
+__device__ __forceinline__ void kl_log_field(const PorousHetDev &h, const double *x, double *kl) {
+  const double *T = h.kl_tab, *C = h.kl_tab + 3 * kKLMax * 3;
+  const int nx = h.n[0], ny = h.n[1], nz = DIM == 3 ? h.n[2] : 1;
+  auto phi = [&](int d, int i, double xd) {
+    const double *t = T + (d * kKLMax + i) * 3;
+    double s, c;
+    sincos(t[0] * xd, &s, &c);
+    return t[1] * c + t[2] * s;
+  };
+  double px[kKLMax], py[kKLMax];
+#pragma unroll
+  for (int i = 0; i < kKLMax; ++i) {
+    px[i] = i < nx ? phi(0, i, x[0]) : 0.0;
+    py[i] = i < ny ? phi(1, i, x[1]) : 0.0;
+  }
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) kl[c] = 0.0;
+  for (int k = 0; k < nz; ++k) {
+    const double pz = DIM == 3 ? phi(2, k, x[DIM - 1]) : 1.0;
+    const double *Ck = C + (size_t)k * kKLMax * kKLMax * 3;
+#pragma unroll
+    for (int j = 0; j < kKLMax; ++j) {
+      if (j >= ny) break;
+      const double pyz = py[j] * pz;
+#pragma unroll
+      for (int i = 0; i < kKLMax; ++i) {
+        if (i >= nx) break;
+        const double t = px[i] * pyz;
+        const double *cc = Ck + (j * kKLMax + i) * 3;
+#pragma unroll
+        for (int c = 0; c < DIM; ++c) kl[c] += cc[c] * t;
+      }
+    }
+  }
+}
+
 inline bool has_expression(const FuncDesc &f) { return f.kind == MHA_FUNC_EXPRESSION; }
 inline bool uses_fields(const FuncDesc &f) { return f.kind == MHA_FUNC_EXPRESSION && f.uses_fields != 0; }
 inline bool has_expression(const ThermalDev &ph) {

@@ -243,11 +243,26 @@ struct ProjectDev {
   const double *basis = nullptr;    // [num][card][np][ncomp]
 };
 
+// porousMixed heterogeneous permeability (reference: porousMixed::updatePerm / updateKLPerm, porousMixed.cpp:550-714).
+// Element data column 0 replaces the Kinv_* functions (Kinv = 1 / data); a Karhunen-Loeve log-field divides Kinv by
+// exp(KL_dd) at every point.  The tables live in device memory and are read with wave-uniform indices.
+constexpr int kKLMax = 8;  // roots per direction the kernels evaluate (MHA_KL_MAX_TERMS; the host refuses more)
+struct PorousHetDev {
+  const double *edata = nullptr;  // [E][ecols], column 0 read; null: the Kinv_* functions
+  int ecols = 0;
+  int kl = 0;                     // 1: the KL field is on
+  int n[3] = {0, 0, 0};           // roots per direction (1 for a direction beyond dim)
+  // [3][kKLMax][3]: per direction and root {omega, eta*omega/norm, 1/norm}, phi(x) = (eta omega cos wx + sin wx) / norm;
+  // then [kKLMax][kKLMax][kKLMax][3]: the coefficient of phi_x,i phi_y,j phi_z,k in KL_xx, KL_yy, KL_zz at [k][j][i]
+  const double *kl_tab = nullptr;
+};
+
 // What a physics module's point function reads besides the fields: its named functions and scalar settings.
 struct PhysParamsDev {
   int physics = 0;
   FuncDesc f[kMaxFuncs];
   double p[8] = {0};
+  PorousHetDev het;  // porousMixed only; read by the heterogeneous instantiations alone
 };
 
 // Row -> (element, LID position) incidences + the element-major slot map (kernels/row_gather.hip).

@@ -62,16 +62,28 @@ __device__ __forceinline__ void thermal_point(const PointArgs<DIM> &a, Dual *F) 
 }
 
 // porousMixed (reference: src/physics/porousMixed.cpp:158-338); myvars {p (HVOL), u (HDIV)};
-// functions {source, Kinv_xx, Kinv_yy, Kinv_zz, total_mobility}
-template <int DIM, bool EXPR>
+// functions {source, Kinv_xx, Kinv_yy, Kinv_zz, total_mobility}; HET: heterogeneous permeability (PorousHetDev) --
+// Kinv = 1 / element data column 0 instead of the functions, then divided by exp of the KL log-field
+template <int DIM, bool EXPR, bool HET = false>
 __device__ __forceinline__ void porous_point(const PointArgs<DIM> &a, Dual *F) {
   const PhysParamsDev &pp = *a.pp;
   const double src = eval_func<DIM, EXPR>(pp.f[0], a.e, a.q, a.nq, a.x), mob = eval_func<DIM, EXPR>(pp.f[4], a.e, a.q, a.nq, a.x);
   const Dual p = a.U[0], divu = a.U[1 + DIM];
   F[0] = mk(src) - divu;  // (source - div u, q)
+  double kl[DIM];
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) kl[d] = 0.0;
+  if constexpr (HET)
+    if (pp.het.kl) kl_log_field<DIM>(pp.het, a.x, kl);
 #pragma unroll
   for (int d = 0; d < DIM; ++d) {
-    const double Kinv = eval_func<DIM, EXPR>(pp.f[1 + d], a.e, a.q, a.nq, a.x);
+    double Kinv;
+    if constexpr (HET) {
+      Kinv = pp.het.edata ? 1.0 / pp.het.edata[(size_t)a.e * pp.het.ecols] : eval_func<DIM, EXPR>(pp.f[1 + d], a.e, a.q, a.nq, a.x);
+      if (pp.het.kl) Kinv = Kinv / exp(kl[d]);
+    } else {
+      Kinv = eval_func<DIM, EXPR>(pp.f[1 + d], a.e, a.q, a.nq, a.x);
+    }
     F[1 + d] = a.U[1 + d] * Kinv / mob;  // ((mobility K)^-1 u, v)
   }
   F[1 + DIM] = -p;  // -(p, div v)

@@ -154,6 +154,7 @@ __host__ __device__ inline size_t engine_group_doubles(const VarLayoutDev &vl, i
 // NQ1 = integration points per direction when it is 2 or 3 (the loops over points then have compile-time bounds and
 // the compiler batches their LDS loads), 0 = taken from the layout at run time.
 template <int DIM, int PHYS, int TPE, int NQ1, int EXPR>  // EXPR: 0 / 1 deck strings / 2 deck strings that read the solution fields (thermal)
+                                                          // / 3 porousMixed with heterogeneous permeability (no deck strings)
 __global__ __launch_bounds__(kEngineThreads) void point_engine_kernel(BlockDev b, VarLayoutDev vl, PhysParamsDev pp,
                                                                       TimeDev tm, ElemOut out_all,
                                                                       const uint8_t *slot8_all, const uint16_t *slot16_all) {
@@ -360,7 +361,7 @@ __global__ __launch_bounds__(kEngineThreads) void point_engine_kernel(BlockDev b
           for (int sl = 0; sl < ns; ++sl) F[sp + sl] = value_like(type, sl, DIM) ? U[sp + sl] * pp.p[v] : mk(0.0);
         }
       } else if constexpr (PHYS == MHA_PHYSICS_THERMAL) thermal_point<DIM, EXPR>(pa, F);
-      else if constexpr (PHYS == MHA_PHYSICS_POROUS_MIXED) porous_point<DIM, (EXPR != 0)>(pa, F);
+      else if constexpr (PHYS == MHA_PHYSICS_POROUS_MIXED) porous_point<DIM, (EXPR == 1), (EXPR == 3)>(pa, F);
       else if constexpr (PHYS == MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED) swhdg_point<DIM, (EXPR != 0)>(pa, F);
       else navierstokes_point<DIM, (EXPR != 0)>(pa, F);
 #pragma unroll
@@ -799,6 +800,15 @@ void launch_typed(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev
       else go(point_engine_kernel<DIM, PHYS, 512, 0, 2>);
     } else {
       MHA_REQUIRE(false, MHA_ERR_INVALID, "functions of the solution fields are built for the thermal module");
+    }
+  } else if (PHYS == MHA_PHYSICS_POROUS_MIXED && (pp.het.edata || pp.het.kl)) {
+    if constexpr (PHYS == MHA_PHYSICS_POROUS_MIXED) {
+      MHA_REQUIRE(!has_expression(pp), MHA_ERR_INVALID,
+                  "porousMixed: heterogeneous permeability with deck-string functions is not built; give source / mobility as constants or closed forms");
+      if (groups == 8) go(point_engine_kernel<DIM, PHYS, 64, 0, 3>);
+      else if (groups == 4) go(point_engine_kernel<DIM, PHYS, 128, 0, 3>);
+      else if (groups == 2) go(point_engine_kernel<DIM, PHYS, 256, 0, 3>);
+      else go(point_engine_kernel<DIM, PHYS, 512, 0, 3>);
     }
   } else if (pp.physics > 0 && has_expression(pp)) {
     // deck-string functions: the interpreter call costs registers and scratch, so only these instantiations carry it

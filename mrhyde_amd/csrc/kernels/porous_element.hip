@@ -34,7 +34,9 @@ namespace {
 constexpr int kPorousThreads = 128;
 constexpr int kPorousResWaves = 2;  // waves per SIMD the lean direct build is compiled for
 
-template <int DIM, bool EXPR, bool DOF, bool DIRECT = false, bool RESONLY = false>
+// HET (heterogeneous permeability, PorousHetDev): 0 the Kinv_* functions; 1 Kinv = 1 / element data; 2 the KL field on
+// top of the data or the functions.  Separate instantiations: the plain ones are compiled exactly as before.
+template <int DIM, bool EXPR, bool DOF, bool DIRECT = false, bool RESONLY = false, int HET = 0>
 __device__ __forceinline__ void porous_element_body(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp,
                                                     const TimeDev &tm, const ElemOut &out) {
   constexpr int NN = 1 << DIM, NU = 2 * DIM, N = 1 + NU;
@@ -130,6 +132,10 @@ __device__ __forceinline__ void porous_element_body(const BlockDev &b, const Var
       sB[d] = sin_moderate(pp.f[0].freq[d] * xb);
     }
   }
+  // element data: one load per element (absolute element, after direct_elist); reference: updatePerm (porousMixed.cpp:550-563)
+  double rdat = 0.0;
+  if constexpr (HET != 0)
+    if (pp.het.edata) rdat = 1.0 / pp.het.edata[(size_t)e * pp.het.ecols];
   auto point_loop = [&](auto jm_tag) {
   constexpr bool JM = decltype(jm_tag)::value;
   for (int q = 0; q < NQ; ++q) {
@@ -167,7 +173,17 @@ __device__ __forceinline__ void porous_element_body(const BlockDev &b, const Var
     const double rmob = 1.0 / mob;  // one division per point instead of fifteen
     double kinv[DIM];
 #pragma unroll
-    for (int d = 0; d < DIM; ++d) kinv[d] = eval_func<DIM, EXPR>(pp.f[1 + d], e, q, NQ, x);
+    for (int d = 0; d < DIM; ++d) {
+      if constexpr (HET == 1) kinv[d] = rdat;
+      else if constexpr (HET == 2) kinv[d] = pp.het.edata ? rdat : eval_func<DIM, EXPR>(pp.f[1 + d], e, q, NQ, x);
+      else kinv[d] = eval_func<DIM, EXPR>(pp.f[1 + d], e, q, NQ, x);
+    }
+    if constexpr (HET == 2) {  // Kinv_dd / exp(KL_dd) (porousMixed.cpp:567-714)
+      double kl[DIM];
+      kl_log_field<DIM>(pp.het, x, kl);
+#pragma unroll
+      for (int d = 0; d < DIM; ++d) kinv[d] = kinv[d] / exp(kl[d]);
+    }
     rp += src * w;
     // unsigned basis: v_i = ph_i J[:,c_i], ph_i = (1 -/+ xi_c)/2 / det
     double ph[NU], uq[DIM];
@@ -348,6 +364,29 @@ __global__ __launch_bounds__(kPorousThreads) void porous_element_direct_expr_ker
                                                                                    TimeDev tm, ElemOut out) {
   porous_element_body<DIM, true, true, true>(b, vl, pp, tm, out);
 }
+// heterogeneous permeability (HET 1 element data, 2 KL field).  The 3-D KL builds run at one wavefront per SIMD, where
+// they need no scratch (at two they spill up to 212 B per lane).  The element-data builds keep the plain builds' two:
+// at one the 3-D direct build took 16 % longer than the plain one at 128^3; at two it spills 52 B per lane where the
+// plain 3-D direct build spills 92 (profiles/porous_heterogeneous.md).
+template <int DIM, int HET>
+constexpr int kPorousHetWaves = (DIM == 3 && HET == 2) ? 1 : 2;
+// the direct form, its lean residual build, and the dense
+// local arrays (both orders; the runtime decides whether data, functions or both feed the KL build)
+template <int DIM, int HET>
+__global__ __launch_bounds__(kPorousThreads, (kPorousHetWaves<DIM, HET>)) void porous_element_direct_het_kernel(
+    BlockDev b, VarLayoutDev vl, PhysParamsDev pp, TimeDev tm, ElemOut out) {
+  porous_element_body<DIM, false, true, true, false, HET>(b, vl, pp, tm, out);
+}
+template <int DIM, int HET>
+__global__ __launch_bounds__(kPorousThreads, (kPorousHetWaves<DIM, HET>)) void porous_element_direct_res_het_kernel(
+    BlockDev b, VarLayoutDev vl, PhysParamsDev pp, TimeDev tm, ElemOut out) {
+  porous_element_body<DIM, false, true, true, true, HET>(b, vl, pp, tm, out);
+}
+template <int DIM, bool DOF>
+__global__ __launch_bounds__(kPorousThreads, (kPorousHetWaves<DIM, 2>)) void porous_element_het_kernel(
+    BlockDev b, VarLayoutDev vl, PhysParamsDev pp, TimeDev tm, ElemOut out) {
+  porous_element_body<DIM, false, DOF, false, false, 2>(b, vl, pp, tm, out);
+}
 
 // ---- database mode on a uniform block: the residual from the element matrix ---------------------------------------------
 // porousMixed is linear: with constant permeability / mobility the volume residual of an element is
@@ -481,6 +520,10 @@ void launch_porous_element(const BlockDev &b, const VarLayoutDev &vl, const Phys
               "porous element kernel writes dense element arrays only");
   const int grid = (b.e_count + kPorousThreads - 1) / kPorousThreads;
   const int n = 1 + 2 * b.dim;
+  const bool het = pp.het.edata != nullptr || pp.het.kl != 0;
+  MHA_REQUIRE(!het || !has_expression(pp), MHA_ERR_INVALID,
+              "porousMixed: heterogeneous permeability with deck-string functions is not built; give source / mobility as constants or closed forms");
+  MHA_REQUIRE(!het || !out.direct_uniform, MHA_ERR_INVALID, "porousMixed: database mode with heterogeneous permeability");
   if (out.direct_part && out.direct_uniform && out.direct_res_only && !has_expression(pp)) {
     launch_porous_uniform_residual(b, vl, pp, tm, out, out.direct_uniform, stream);
     return;
@@ -489,6 +532,18 @@ void launch_porous_element(const BlockDev &b, const VarLayoutDev &vl, const Phys
     MHA_REQUIRE(out.direct_slot != nullptr && out.direct_side != nullptr && out.local_base == 0, MHA_ERR_INVALID, "porous direct form: slot map missing");
     const size_t ldsd = sizeof(double) * kPorousThreads * (size_t)(1 << b.dim) * b.dim;
     auto god = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(kPorousThreads), ldsd, stream, b, vl, pp, tm, out); };
+    if (het) {
+      const bool res = out.direct_res_only != 0, kl = pp.het.kl != 0;
+      if (b.dim == 2) {
+        if (res) { if (kl) god(porous_element_direct_res_het_kernel<2, 2>); else god(porous_element_direct_res_het_kernel<2, 1>); }
+        else { if (kl) god(porous_element_direct_het_kernel<2, 2>); else god(porous_element_direct_het_kernel<2, 1>); }
+      } else {
+        if (res) { if (kl) god(porous_element_direct_res_het_kernel<3, 2>); else god(porous_element_direct_res_het_kernel<3, 1>); }
+        else { if (kl) god(porous_element_direct_het_kernel<3, 2>); else god(porous_element_direct_het_kernel<3, 1>); }
+      }
+      MHA_HIP(hipGetLastError());
+      return;
+    }
     if (out.direct_res_only && !has_expression(pp)) { if (b.dim == 2) god(porous_element_direct_res_kernel<2>); else god(porous_element_direct_res_kernel<3>); }
     else if (has_expression(pp)) { if (b.dim == 2) god(porous_element_direct_expr_kernel<2>); else god(porous_element_direct_expr_kernel<3>); }
     else { if (b.dim == 2) god(porous_element_direct_kernel<2>); else god(porous_element_direct_kernel<3>); }
@@ -503,7 +558,9 @@ void launch_porous_element(const BlockDev &b, const VarLayoutDev &vl, const Phys
   auto pick = [&](auto dim_c, auto dof_c) {
     constexpr int D = decltype(dim_c)::value;
     constexpr bool F = decltype(dof_c)::value;
-    if (expr) go(porous_element_expr_kernel<D, F>); else go(porous_element_kernel<D, F>);
+    if (het) go(porous_element_het_kernel<D, F>);
+    else if (expr) go(porous_element_expr_kernel<D, F>);
+    else go(porous_element_kernel<D, F>);
   };
   if (b.dim == 2) { if (dof) pick(std::integral_constant<int, 2>(), std::true_type()); else pick(std::integral_constant<int, 2>(), std::false_type()); }
   else { if (dof) pick(std::integral_constant<int, 3>(), std::true_type()); else pick(std::integral_constant<int, 3>(), std::false_type()); }

@@ -73,6 +73,12 @@ class PhysicsBase {
   virtual void setParameter(const std::string &name, double) {
     throw Error(MHA_ERR_INVALID, "physics module '" + label + "' has no parameter '" + name + "'");
   }
+  // vector-valued parameters the reference module reads from the workset (wkset->getParameter)
+  virtual void setParameterVector(const std::string &name, const double *, int) {
+    throw Error(MHA_ERR_INVALID, "physics module '" + label + "' has no parameter vector '" + name + "'");
+  }
+  // true when the coefficients differ from element to element in a way the geometry database cannot see
+  virtual bool heterogeneous() const { return false; }
 
   std::string label;
   Workset *wkset = nullptr;
@@ -105,6 +111,11 @@ class thermal : public PhysicsBase {
 
 // porousMixed: mixed Darcy, (K mobility)^-1 u + grad p = 0, div u = source
 // (reference: src/physics/porousMixed.hpp, src/physics/porousMixed.cpp:24-432); myvars {p (HVOL), u (HDIV)}
+// Heterogeneous permeability (porousMixed.cpp:46-120, 550-714): "use permeability data" takes Kinv_xx = Kinv_yy = Kinv_zz
+// = 1 / data(elem, 0) from the element data of the block (Workset::elem_data); "use KL expansion" divides Kinv_dd by
+// exp(KL_dd), a Karhunen-Loeve field with one 1-D expansion per direction ("KL N x", "KL L x", "KL sigma x", "KL eta x",
+// ...) and the coefficient vectors "KLUQcoeffs" / "KLStochcoeffs".  The device tables (PorousHetDev) are rebuilt when a
+// setting or a vector changes, at the next assembly.
 class porousMixed : public PhysicsBase {
  public:
   porousMixed();
@@ -112,6 +123,23 @@ class porousMixed : public PhysicsBase {
   void volumeResidual() override;
   void boundaryResidual() override;
   void computeFlux() override;
+  void setParameter(const std::string &name, double value) override;
+  void setParameterVector(const std::string &name, const double *v, int n) override;
+  bool heterogeneous() const override { return usePermData || useKL; }
+  bool usePermData = false, useKL = false;
+  // false reproduces the 3-D KLUQcoeffs branch of updateKLPerm (porousMixed.cpp:614-637): lambda_z from the y expansion,
+  // the term added twice to KL_xx, once to KL_yy, never to KL_zz
+  bool fix_KL_3d = false;
+
+ private:
+  PorousHetDev hetParams();
+  void buildKLTables(int dim);
+  int klN_[3] = {-1, -1, -1};
+  double klL_[3] = {0, 0, 0}, klSigma_[3] = {0, 0, 0}, klEta_[3] = {0, 0, 0};
+  bool klSet_[3][3] = {};  // L, sigma, eta given per direction
+  std::vector<double> uq_, stoch_;
+  bool hasUQ_ = false, hasStoch_ = false, klDirty_ = true;
+  DeviceBuffer<double> klTab_;
 };
 
 // navierstokes: incompressible Navier-Stokes with optional SUPG / PSPG

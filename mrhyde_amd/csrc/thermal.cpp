@@ -3,6 +3,10 @@
 #include "physics.hpp"
 
 #include "expression.hpp"
+#include "porous_data.hpp"
+
+#include <cmath>
+#include <cstring>
 
 #include <cstdlib>
 
@@ -225,6 +229,7 @@ void porousMixed::volumeResidual() {
   pp.physics = MHA_PHYSICS_POROUS_MIXED;
   const char *names[5] = {"source", "Kinv_xx", "Kinv_yy", "Kinv_zz", "total_mobility"};
   for (int k = 0; k < 5; ++k) pp.f[k] = functionManager->evaluate(names[k]);
+  pp.het = hetParams();
   // dense element arrays (row-gather path, mha_compute_local_jacres): the thread-per-element kernel; global outputs
   // (atomic scatter): the point engine.  MHA_POROUS_KERNEL=engine forces the engine.
   static const bool force_engine = [] { const char *m = std::getenv("MHA_POROUS_KERNEL"); return m && m[0] == 'e'; }();
@@ -232,6 +237,119 @@ void porousMixed::volumeResidual() {
     launch_porous_element(b, w.layout, pp, w.time_dev, w.res, w.stream);
   else
     launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+}
+
+// reference: porousMixed constructor settings (porousMixed.cpp:46-120): "use permeability data", "use KL expansion" and the
+// "KL parameters" sublist flattened to "KL N x", "KL L x", "KL sigma x", "KL eta x" (y, z alike); "fix_KL_3d" is ours
+void porousMixed::setParameter(const std::string &name, double value) {
+  const char *klkeys[4] = {"KL N ", "KL L ", "KL sigma ", "KL eta "};
+  if (name == "use permeability data") { usePermData = value != 0.0; return; }
+  if (name == "use KL expansion") { useKL = value != 0.0; klDirty_ = true; return; }
+  if (name == "fix_KL_3d") { fix_KL_3d = value != 0.0; klDirty_ = true; return; }
+  for (int k = 0; k < 4; ++k) {
+    const size_t n = std::strlen(klkeys[k]);
+    if (name.size() == n + 1 && name.compare(0, n, klkeys[k]) == 0 && name[n] >= 'x' && name[n] <= 'z') {
+      const int d = name[n] - 'x';
+      if (k == 0) {
+        MHA_REQUIRE(value >= 1 && value <= kKLMax && value == std::floor(value), MHA_ERR_INVALID,
+                    "porousMixed: '" << name << "' must be an integer in 1.." << kKLMax << " (the kernels' cap per direction)");
+        klN_[d] = static_cast<int>(value);
+      } else {
+        MHA_REQUIRE(std::isfinite(value) && (k == 2 || value > 0.0), MHA_ERR_INVALID, "porousMixed: bad value for '" << name << "'");
+        (k == 1 ? klL_ : k == 2 ? klSigma_ : klEta_)[d] = value;
+        klSet_[d][k - 1] = true;
+      }
+      klDirty_ = true;
+      return;
+    }
+  }
+  PhysicsBase::setParameter(name, value);
+}
+
+// reference: wkset->getParameter("KLUQcoeffs") / ("KLStochcoeffs") in updateKLPerm (porousMixed.cpp:573, 642)
+void porousMixed::setParameterVector(const std::string &name, const double *v, int n) {
+  MHA_REQUIRE(name == "KLUQcoeffs" || name == "KLStochcoeffs", MHA_ERR_INVALID,
+              "porousMixed has no parameter vector '" << name << "' (KLUQcoeffs, KLStochcoeffs)");
+  MHA_REQUIRE(n >= 0 && (n == 0 || v), MHA_ERR_INVALID, "parameter vector '" << name << "': null values");
+  for (int k = 0; k < n; ++k) MHA_REQUIRE(std::isfinite(v[k]), MHA_ERR_INVALID, "parameter vector '" << name << "': non-finite value");
+  (name == "KLUQcoeffs" ? uq_ : stoch_).assign(v, v + n);
+  (name == "KLUQcoeffs" ? hasUQ_ : hasStoch_) = true;
+  klDirty_ = true;
+}
+
+// The device tables of the KL field (PorousHetDev::kl_tab): per direction and root {omega, eta omega / norm, 1 / norm};
+// then the terms of updateKLPerm folded into one coefficient per (i, j, k) and component:
+//   KLUQcoeffs    terms 0 .. min(len, nidx)            c sqrt(lambda_x lambda_y lambda_z) -> (xx, yy, zz) x multiplicity
+//   KLStochcoeffs terms prog .. min(nidx, prog + len)  prog = len(KLUQcoeffs) if that vector is set
+// with the 3-D quirk of the KLUQcoeffs branch unless fix_KL_3d.
+void porousMixed::buildKLTables(int dim) {
+  const char dn[3] = {'x', 'y', 'z'};
+  const char *what[3] = {"L", "sigma", "eta"};
+  double omega[3][kKLMax] = {}, lambda[3][kKLMax] = {};
+  std::vector<double> tab(static_cast<size_t>(3) * kKLMax * 3 + static_cast<size_t>(kKLMax) * kKLMax * kKLMax * 3, 0.0);
+  int N[3] = {1, 1, 1};
+  for (int d = 0; d < dim; ++d) {
+    MHA_REQUIRE(klN_[d] >= 1, MHA_ERR_INVALID, "porousMixed: 'use KL expansion' needs 'KL N " << dn[d] << "'");
+    for (int k = 0; k < 3; ++k)
+      MHA_REQUIRE(klSet_[d][k], MHA_ERR_INVALID, "porousMixed: 'use KL expansion' needs 'KL " << what[k] << " " << dn[d] << "'");
+    N[d] = klN_[d];
+    const int found = kl_roots(N[d], klL_[d], klSigma_[d], klEta_[d], omega[d], lambda[d]);
+    MHA_REQUIRE(found == N[d], MHA_ERR_INVALID,
+                "porousMixed: the KL expansion in " << dn[d] << " found " << found << " of " << N[d] << " roots");
+    for (int i = 0; i < N[d]; ++i) {
+      const double rn = 1.0 / kl_norm(omega[d][i], klL_[d], klEta_[d]);
+      double *t = &tab[(static_cast<size_t>(d) * kKLMax + i) * 3];
+      t[0] = omega[d][i];
+      t[1] = klEta_[d] * omega[d][i] * rn;
+      t[2] = rn;
+    }
+  }
+  std::vector<int32_t> idx;
+  kl_indices(dim, N, idx);
+  const size_t nidx = idx.size() / dim;
+  double *C = tab.data() + static_cast<size_t>(3) * kKLMax * 3;
+  auto add = [&](size_t t, double c, bool uq) {
+    const int i = idx[t * dim], j = idx[t * dim + 1], k = dim == 3 ? idx[t * dim + 2] : 0;
+    const bool quirk = uq && dim == 3 && !fix_KL_3d;
+    MHA_REQUIRE(!quirk || k < N[1], MHA_ERR_INVALID,
+                "porousMixed: KLUQcoeffs in 3-D take lambda_z from the y expansion (as the reference does): 'KL N z' must not "
+                "exceed 'KL N y' unless fix_KL_3d is set");
+    double lam = lambda[0][i] * lambda[1][j];
+    if (dim == 3) lam *= quirk ? lambda[1][k] : lambda[2][k];
+    const double a = c * std::sqrt(lam);
+    const double mult[3] = {quirk ? 2.0 : 1.0, 1.0, quirk ? 0.0 : 1.0};
+    double *cc = C + ((static_cast<size_t>(k) * kKLMax + j) * kKLMax + i) * 3;
+    for (int comp = 0; comp < dim; ++comp) cc[comp] += mult[comp] * a;
+  };
+  size_t prog = 0;
+  if (hasUQ_) {
+    for (size_t t = 0; t < std::min(uq_.size(), nidx); ++t) add(t, uq_[t], true);
+    prog = uq_.size();
+  }
+  if (hasStoch_)
+    for (size_t t = prog; t < std::min(nidx, prog + stoch_.size()); ++t) add(t, stoch_[t - prog], false);
+  // an assembly queued earlier on the stream may still read the old tables
+  MHA_HIP(hipStreamSynchronize(wkset->stream));
+  klTab_.upload(tab);
+  klDirty_ = false;
+}
+
+PorousHetDev porousMixed::hetParams() {
+  PorousHetDev h;
+  Workset &w = *wkset;
+  if (usePermData) {
+    MHA_REQUIRE(w.elem_data != nullptr, MHA_ERR_STATE,
+                "porousMixed: 'use permeability data' is set but the block has no element data (mha_set_element_data / mha_import_mesh_data)");
+    h.edata = w.elem_data;
+    h.ecols = w.elem_data_cols;
+  }
+  if (useKL) {
+    if (klDirty_) buildKLTables(w.dev.dim);
+    h.kl = 1;
+    for (int d = 0; d < 3; ++d) h.n[d] = d < w.dev.dim ? klN_[d] : 1;
+    h.kl_tab = klTab_.data();
+  }
+  return h;
 }
 
 // reference: porousMixed::boundaryResidual (porousMixed.cpp:345-432): bcs(pnum, side) == "Dirichlet" adds

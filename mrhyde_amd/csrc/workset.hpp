@@ -56,6 +56,9 @@ class Workset {
   bool single_hgrad = true;  // basis / basis_grad views exist for single-variable HGRAD blocks only
   hipStream_t stream = nullptr;
   int order = 0, nq1 = 0;
+  // element data of the block, [E][elem_data_cols] in mesh element order (reference: groups->data, wkset->extra_data)
+  const double *elem_data = nullptr;
+  int elem_data_cols = 0;
 
   // --- boundary state (reference: wkset->sidename / currentside / var_bcs, set by updateWorksetBoundary,
   // assemblyManager.cpp:5646-5710) ---
