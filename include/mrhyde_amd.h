@@ -63,7 +63,9 @@ typedef struct mha_block_desc {
   int dimension;                 /* 2 or 3                                      */
   int topology;                  /* MHA_TOPO_QUAD4 / MHA_TOPO_HEX8              */
   int num_vars;                  /* thermal: 1 ("e"); porousMixed: 2 ("p","u");
-                                    navierstokes: dim+1 ("ux","pr","uy"[,"uz"])  */
+                                    navierstokes: dim+1 ("ux","pr","uy"[,"uz"]);
+                                    navierstokes + thermal: dim+2
+                                    ("ux","pr","uy"[,"uz"],"e")                  */
   int basis_type[MHA_MAX_VARS];  /* MHA_BASIS_*, in the module's myvars order    */
   int basis_order[MHA_MAX_VARS]; /* Discretization: order                       */
   int quadrature_degree;         /* Discretization: quadrature (0 => 2*max order,
@@ -108,6 +110,20 @@ int mha_get_graph(mha_context *ctx, int32_t *rowptr_host, int32_t *colind_host);
 #define MHA_PHYSICS_NAVIERSTOKES 3   /* src/physics/navierstokes.cpp: ux, pr, uy[, uz] (HGRAD)                */
 #define MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED 4 /* src/physics/shallowwaterHybridized.cpp: H, Hux, Huy (HGRAD, 2-D):
                                                 volumeResidual only; the side terms are mha_swhdg_side_terms */
+/* The reference's `modules: navierstokes, thermal` on ONE block (Boussinesq coupling, natural convection).  Variables,
+ * all HGRAD, in the order of the reference's variable list when navierstokes is imported before thermal:
+ * ux, pr, uy[, uz], e (num_vars = dim + 2).  navierstokes finds "e" (navierstokes::setWorkset, navierstokes.cpp:1026-1046:
+ * have_energy) and adds the buoyancy terms density * beta * (e - T_ambient) * source_i to the momentum rows and to their
+ * SUPG / PSPG parts (:283-…, 368-…, 471-… in 2-D, :529-…, 619-632, 654-671, 709-722, 744-761, 824-845 in 3-D); thermal
+ * finds "ux" (thermal::setWorkset, thermal.cpp:359-379: have_nsvel) and adds (u . grad e, v) (:117-121, 139-149).
+ * Functions: the six of navierstokes (navierstokes.cpp:68-74) and "thermal source", "thermal diffusion", "specific heat",
+ * "bx", "by", "bz" (thermal.cpp:52-63); "density" is ONE function read by both modules (FunctionManager::addFunction
+ * keeps the first tree of a name, functionManager.cpp:48-68).  Parameters: useSUPG, usePSPG, fix_uz_offsets, T_ambient
+ * (0), beta (1) (navierstokes.cpp:45-53), "include advection" (0; thermal.cpp:39).  Volume terms only: thermal boundary
+ * groups (Neumann, weak Dirichlet, interface) and computeFlux on this block are refused with MHA_ERR_INVALID; strong
+ * Dirichlet rows and the generic "Flux" condition work per variable as on every block.  Deck strings in the
+ * coordinates are accepted; deck strings that read the solution fields are refused.                              */
+#define MHA_PHYSICS_NAVIERSTOKES_THERMAL 5
 int mha_physics_select(mha_context *ctx, int physics_id);
 #define MHA_FUNC_CONSTANT 0
 #define MHA_FUNC_IP_ARRAY 1     /* dev pointer to [E][numip] f64                    */

@@ -482,8 +482,15 @@ void AssemblyManager::selectPhysics(int physics_id) {
   else if (physics_id == MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED)
     MHA_REQUIRE(dim_ == 2 && expect({MHA_BASIS_HGRAD, MHA_BASIS_HGRAD, MHA_BASIS_HGRAD}), MHA_ERR_INVALID,
                 "shallowwaterHybridized needs the HGRAD variables H, Hux, Huy in 2-D");
+  else if (physics_id == MHA_PHYSICS_NAVIERSTOKES_THERMAL) {
+    bool ok = static_cast<int>(vars_.size()) == dim_ + 2;
+    for (const auto &vi : vars_) ok = ok && vi.type == MHA_BASIS_HGRAD;
+    MHA_REQUIRE(ok, MHA_ERR_INVALID,
+                "navierstokes+thermal needs the " << dim_ + 2 << " HGRAD variables ux, pr, uy" << (dim_ == 3 ? ", uz" : "")
+                                                   << ", e, in that order");
+  }
   physics_id_ = physics_id;
-  physics_ = import_physics(physics_id);
+  physics_ = import_physics(physics_id, dim_);
   physics_->defineFunctions(functions_);
   physics_->setWorkset(&wkset_);
   // names of the solution fields a deck string may read (Workset::getSolutionField, workset.cpp:314-379) -> slots of
@@ -1447,6 +1454,10 @@ int AssemblyManager::addBoundaryGroup(const std::string &sidename, int bc_type, 
               MHA_ERR_INVALID, "boundary-condition type must be one of MHA_BC_*");
   MHA_REQUIRE(num >= 0 && (num == 0 || (elem_ids && side_ids)), MHA_ERR_INVALID, "bad boundary entry arrays");
   MHA_REQUIRE(!sidename.empty(), MHA_ERR_INVALID, "side name is empty");
+  // the thermal boundary kernels are written for a one-variable block: refused, not run against the wrong variable
+  MHA_REQUIRE(physics_id_ != MHA_PHYSICS_NAVIERSTOKES_THERMAL, MHA_ERR_INVALID,
+              "navierstokes+thermal: thermal boundary groups (Neumann, weak Dirichlet, interface on e) are not built for "
+              "the coupled block; strong Dirichlet rows and the generic Flux condition are");
   prepareSideTables();
   for (int k = 0; k < num; ++k) {
     MHA_REQUIRE(elem_ids[k] >= 0 && elem_ids[k] < nelem_, MHA_ERR_INVALID,
@@ -1621,6 +1632,11 @@ void AssemblyManager::assembleBoundary(int flags, const double *u, const double 
   MHA_REQUIRE(res != nullptr, MHA_ERR_INVALID, "residual vector is null");
   MHA_REQUIRE(!compute_jacobian || crs_vals, MHA_ERR_INVALID, "compute_jacobian set but crs_vals is null");
   bindState(u, u_prev, u_stage);
+  // (groups added before the coupled module was selected: refused before anything is written)
+  if (physics_id_ == MHA_PHYSICS_NAVIERSTOKES_THERMAL)
+    for (const auto &g : boundary_groups_)
+      MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX, MHA_ERR_INVALID,
+                  "navierstokes+thermal: thermal boundary groups are not built for the coupled block (group '" << g->sidename << "')");
   timedBegin();
   for (size_t gi = 0; gi < boundary_groups_.size(); ++gi) {
     const auto &g = boundary_groups_[gi];

@@ -192,7 +192,10 @@ struct BoundaryViewsDev {
 };
 
 // ---- multi-variable blocks (kernels/point_engine.hip) -------------------------------------------------------------
-constexpr int kMaxVars = 8, kMaxSlots = 24, kMaxFuncs = 8;
+// kMaxFuncs: the coupled navierstokes + thermal module names twelve functions.  PhysParamsDev travels by value as a kernel
+// argument (80 B per FuncDesc): the point engine's argument block is 1 808 B with twelve (1 488 B with eight), of the
+// 4 096 B a HIP kernel may take
+constexpr int kMaxVars = 8, kMaxSlots = 24, kMaxFuncs = 12;
 
 // Variables of a block and their "slots": the quantities of a basis function that enter a weak form --
 // HGRAD: value, d/dx, d/dy(, d/dz); HVOL: value; HDIV: the vector components, then the divergence.

@@ -152,6 +152,97 @@ __device__ __forceinline__ void navierstokes_point(const PointArgs<DIM> &a, Dual
   }
 }
 
+// navierstokes + thermal on one block (Boussinesq coupling; reference: navierstokes::setWorkset :1026-1046 sets
+// have_energy when the block has a variable "e", thermal::setWorkset thermal.cpp:359-379 sets have_nsvel when it has
+// "ux"); myvars {ux, pr, uy[, uz], e}; functions {source ux, source pr, source uy, source uz, density, viscosity,
+// thermal source, thermal diffusion, specific heat, bx, by, bz} -- "density" is ONE function read by both modules
+// (FunctionManager::addFunction keeps the first tree of a name, functionManager.cpp:48-68);
+// p = {useSUPG, usePSPG, fix_uz_offsets, T_ambient, beta, include advection}.
+// With g_i = beta (e - T_ambient) source_i the momentum rows get the navierstokes terms plus
+//   value slot      + density g_i                         (navierstokes.cpp:283-296, 368-381, 529-…, 619-632, 709-722)
+//   SUPG            + tau (density g_i) u_d on slot d      (:318-334, 402-418, 654-671, 744-761)
+//   PSPG, pr row    + tau density g_d on slot d            (:471-488, 824-845)
+// and the energy row is thermal's with (u . grad e, v) added (thermal.cpp:139-149).  Its own function: the two modules'
+// point functions above compile exactly as without it.
+template <int DIM, bool EXPR>
+__device__ __forceinline__ void navierstokes_thermal_point(const PointArgs<DIM> &a, Dual *F) {
+  constexpr int S = 1 + DIM;                 // slots per HGRAD variable
+  constexpr int vnum[3] = {0, 2, 3}, prnum = 1, eb = (DIM + 1) * S;  // eb: first slot of e
+  const PhysParamsDev &pp = *a.pp;
+  const bool useSUPG = pp.p[0] != 0.0, usePSPG = pp.p[1] != 0.0, fix_uz = pp.p[2] != 0.0;
+  const double T_ambient = pp.p[3], beta = pp.p[4];
+  auto fn = [&](int k) { return eval_func<DIM, EXPR>(pp.f[k], a.e, a.q, a.nq, a.x); };
+  const double dens = fn(4), visc = fn(5);
+  const double src[3] = {fn(0), fn(2), DIM == 3 ? fn(3) : 0.0};
+  Dual vel[DIM];
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) vel[d] = a.U[vnum[d] * S];
+  const Dual pr = a.U[prnum * S];
+  const Dual bt = (a.U[eb] - T_ambient) * (beta * dens);  // density beta (e - T_ambient)
+  Dual tau = mk(0.0);
+  if (useSUPG || usePSPG) {  // computeTau (navierstokes.cpp:1054-1079)
+    const double C1 = 4.0, C2 = 2.0, C3 = a.transient ? 2.0 : 0.0;
+    Dual nvel = mk(0.0);
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) nvel += vel[d] * vel[d];
+    if (nvel.v > 1e-12) nvel = dsqrt(nvel);
+    const Dual t2 = nvel * (C2 / a.h);
+    const double c1 = C1 * visc / a.h / a.h, c3 = C3 / a.dt;
+    tau = 1.0 / dsqrt(t2 * t2 + (c1 * c1 + c3 * c3));
+  }
+  Dual stab[DIM], buoy[DIM];
+  Dual divu = mk(0.0);
+#pragma unroll
+  for (int i = 0; i < DIM; ++i) {
+    const int b = vnum[i] * S;
+    Dual conv = mk(0.0);
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) conv += vel[d] * a.U[b + 1 + d];
+    const Dual acc = a.Ud[b] + conv;
+    buoy[i] = bt * src[i];
+    F[b] = (acc - src[i]) * dens + buoy[i];
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) {
+      F[b + 1 + d] = a.U[b + 1 + d] * visc;
+      if (d == i) F[b + 1 + d] -= pr;
+    }
+    divu += a.U[b + 1 + i];
+    if (useSUPG || usePSPG) stab[i] = acc * dens + a.U[prnum * S + 1 + i] - dens * src[i];
+    if (useSUPG) {
+      const Dual ts = tau * (stab[i] + buoy[i]);
+#pragma unroll
+      for (int d = 0; d < DIM; ++d) F[b + 1 + d] += ts * vel[d];
+    }
+  }
+  F[prnum * S] = divu;
+  // the buoyancy part of the PSPG term is NOT divided by the density, unlike the part next to it (navierstokes.cpp:480-483
+  // and :833-838 against :462-465 and :813-818): the reference's behaviour, reproduced
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) F[prnum * S + 1 + d] = usePSPG ? stab[d] * tau / dens + tau * buoy[d] : mk(0.0);
+  if (DIM == 3 && !fix_uz) {
+    // the reference scatters the uz momentum block through uy's offsets (navierstokes.cpp:688 is the `off` of :690-761):
+    // the whole block, buoyancy and its SUPG part included, lands on uy's rows; uz's rows stay empty
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      F[vnum[1] * S + s] += F[vnum[DIM - 1] * S + s];
+      F[vnum[DIM - 1] * S + s] = mk(0.0);
+    }
+  }
+  // energy row (thermal.cpp:125-163): rho cp de/dt - source, kappa grad e, then (u . grad e, v) WITHOUT rho cp
+  // (have_nsvel, :139-149) and (b . grad e, v) when "include advection" is set (:150-160)
+  const double f = fn(6), kap = fn(7), cp = fn(8);
+  F[eb] = a.Ud[eb] * (dens * cp) - f;
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    F[eb + 1 + d] = a.U[eb + 1 + d] * kap;
+    F[eb] += vel[d] * a.U[eb + 1 + d];
+  }
+  if (pp.p[5] != 0.0) {
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) F[eb] += a.U[eb + 1 + d] * fn(9 + d);
+  }
+}
+
 // shallowwaterHybridized (reference: src/physics/shallowwaterHybridized.cpp:113-184 with computeFluxVector(false)
 // :409-480); myvars {H, Hux, Huy} (2-D); functions {source H, source Hux, source Huy}; p = {g}
 template <int DIM, bool EXPR>

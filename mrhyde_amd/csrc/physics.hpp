@@ -155,6 +155,27 @@ class navierstokes : public PhysicsBase {
   bool fix_uz_offsets = false;            // false reproduces navierstokes.cpp:688
 };
 
+// navierstokes + thermal on one block: the reference's `modules: navierstokes, thermal` (Boussinesq coupling).  The two
+// modules find each other through the block's variable list -- navierstokes::setWorkset (navierstokes.cpp:1026-1046) sets
+// have_energy when it holds "e", thermal::setWorkset (thermal.cpp:359-379) sets have_nsvel when it holds "ux" -- and share
+// the function "density" (FunctionManager::addFunction keeps the first tree of a name, functionManager.cpp:48-68).
+// myvars {ux, pr, uy[, uz], e}: the variable list when navierstokes is imported before thermal.  Volume terms only: thermal
+// boundary groups and computeFlux on this block are refused (kernels/thermal_boundary.hip is written for a one-variable
+// block).
+class navierstokesThermal : public PhysicsBase {
+ public:
+  explicit navierstokesThermal(int dim);
+  void defineFunctions(FunctionManager &fm) override;
+  void volumeResidual() override;
+  void boundaryResidual() override;
+  void computeFlux() override;
+  void setParameter(const std::string &name, double value) override;
+  bool useSUPG = false, usePSPG = false;  // navierstokes.cpp:45-46
+  bool fix_uz_offsets = false;            // false reproduces navierstokes.cpp:688
+  double T_ambient = 0.0, beta = 1.0;     // navierstokes.cpp:48-53 (model_params)
+  bool have_advection = false;            // thermal.cpp:39: adds (b . grad e, v) on top of (u . grad e, v)
+};
+
 // shallowwaterHybridized: HDG shallow water, interior unknowns H, Hux, Huy; the trace unknowns are the module's "aux"
 // variables (reference: src/physics/shallowwaterHybridized.hpp, .cpp:24-844).  volumeResidual runs on the point engine;
 // the side terms (computeFlux, boundaryResidual's fluxes) are the stateless batch entry point mha_swhdg_side_terms:
@@ -171,6 +192,7 @@ class shallowwaterHybridized : public PhysicsBase {
 };
 
 // PhysicsImporter::import equivalent (reference: src/physics/physicsImporter.cpp:48-204)
-std::unique_ptr<PhysicsBase> import_physics(int physics_id);
+// (dim: the coupled module's variable list depends on it)
+std::unique_ptr<PhysicsBase> import_physics(int physics_id, int dim = 3);
 
 }  // namespace mha

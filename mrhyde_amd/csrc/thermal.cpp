@@ -425,6 +425,71 @@ void navierstokes::volumeResidual() {
   launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
 }
 
+// ---- navierstokes + thermal on one block -------------------------------------------------------------------------
+navierstokesThermal::navierstokesThermal(int dim) {
+  label = "navierstokes+thermal";
+  if (dim == 2) myvars = {"ux", "pr", "uy", "e"};  // navierstokes.cpp:27-34 followed by thermal.cpp:31
+  else myvars = {"ux", "pr", "uy", "uz", "e"};
+  mybasistypes.assign(myvars.size(), "HGRAD");
+}
+
+// both modules' defineFunctions (navierstokes.cpp:62-76, thermal.cpp:52-63) on one function manager: "density" is
+// registered once and read by both
+void navierstokesThermal::defineFunctions(FunctionManager &fm) {
+  functionManager = &fm;
+  auto constant = [](double v) { FuncDesc f; f.kind = MHA_FUNC_CONSTANT; f.amp = v; return f; };
+  for (const char *k : {"source ux", "source pr", "source uy", "source uz", "thermal source", "bx", "by", "bz"})
+    if (!fm.has(k)) fm.addFunction(k, constant(0.0));
+  for (const char *k : {"density", "viscosity", "thermal diffusion", "specific heat"})
+    if (!fm.has(k)) fm.addFunction(k, constant(1.0));
+}
+
+void navierstokesThermal::setParameter(const std::string &name, double value) {
+  if (name == "useSUPG") useSUPG = value != 0.0;
+  else if (name == "usePSPG") usePSPG = value != 0.0;
+  else if (name == "fix_uz_offsets") fix_uz_offsets = value != 0.0;
+  else if (name == "T_ambient") T_ambient = value;
+  else if (name == "beta") beta = value;
+  else if (name == "include advection") have_advection = value != 0.0;
+  else PhysicsBase::setParameter(name, value);
+}
+
+// navierstokes::volumeResidual with have_energy and thermal::volumeResidual with have_nsvel as ONE point function
+// (navierstokes_thermal_point): the e-columns of the momentum rows and the velocity-columns of the energy row come out of
+// the same forward-AD pass
+void navierstokesThermal::volumeResidual() {
+  MHA_REQUIRE(wkset != nullptr, MHA_ERR_STATE, "navierstokes+thermal::volumeResidual called without a workset");
+  Workset &w = *wkset;
+  BlockDev b = w.dev;
+  b.e_begin = w.first_elem;
+  b.e_count = w.numElem;
+  PhysParamsDev pp;
+  pp.physics = MHA_PHYSICS_NAVIERSTOKES_THERMAL;
+  const char *names[12] = {"source ux", "source pr", "source uy", "source uz", "density", "viscosity",
+                           "thermal source", "thermal diffusion", "specific heat", "bx", "by", "bz"};
+  static_assert(kMaxFuncs >= 12, "the coupled module names twelve functions");
+  for (int k = 0; k < 12; ++k) pp.f[k] = functionManager->evaluate(names[k]);
+  pp.p[0] = useSUPG ? 1.0 : 0.0;
+  pp.p[1] = usePSPG ? 1.0 : 0.0;
+  pp.p[2] = fix_uz_offsets ? 1.0 : 0.0;
+  pp.p[3] = T_ambient;
+  pp.p[4] = beta;
+  pp.p[5] = have_advection ? 1.0 : 0.0;
+  launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+}
+
+// thermal::boundaryResidual / computeFlux act on "e" through kernels written for a one-variable block: out of scope
+// here, and refused rather than run against the wrong variable
+void navierstokesThermal::boundaryResidual() {
+  throw Error(MHA_ERR_INVALID,
+              "navierstokes+thermal: thermal boundary groups (Neumann, weak Dirichlet, interface on e) are not built for "
+              "the coupled block; strong Dirichlet rows and the generic Flux condition are");
+}
+
+void navierstokesThermal::computeFlux() {
+  throw Error(MHA_ERR_INVALID, "navierstokes+thermal: computeFlux is not built for the coupled block");
+}
+
 // ---- shallowwaterHybridized --------------------------------------------------------------------------------------
 shallowwaterHybridized::shallowwaterHybridized() {
   label = "shallowwaterHybridized";
@@ -483,7 +548,8 @@ void shallowwaterHybridized::boundaryResidual() {
   launch_swhdg_boundary(w.dev, w.side_tables, w.bnd, sw, w.time_dev, w.res, w.stream);
 }
 
-std::unique_ptr<PhysicsBase> import_physics(int physics_id) {
+std::unique_ptr<PhysicsBase> import_physics(int physics_id, int dim) {
+  if (physics_id == MHA_PHYSICS_NAVIERSTOKES_THERMAL) return std::unique_ptr<PhysicsBase>(new navierstokesThermal(dim));
   if (physics_id == MHA_PHYSICS_THERMAL) return std::unique_ptr<PhysicsBase>(new thermal());
   if (physics_id == MHA_PHYSICS_POROUS_MIXED) return std::unique_ptr<PhysicsBase>(new porousMixed());
   if (physics_id == MHA_PHYSICS_NAVIERSTOKES) return std::unique_ptr<PhysicsBase>(new navierstokes());
