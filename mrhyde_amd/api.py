@@ -534,6 +534,36 @@ def block_pattern_rep_plan(dim, nodes, lids, nrows, rowptr, colind, khat, factor
     return full, rep, stores, expect, units[:info["items"]], part_tiles[:info["parts"]], info
 
 
+def block_pattern_step_plan(dim, nodes, lids, nrows, rowptr, colind, khat, factors, fixed=None, scale_u=1.0, scale_t=1.0,
+                            chunk_elems=16, num_cus=8, max_patterns=256):
+    """Host-only test hook: the geometry-database step with kept representatives.  The representatives' items store into
+    their own compact buffer; the separate-source copy plan then writes every CRS entry from it (each load checked
+    against the buffer).  -> (vals_full: every row block assembled, vals_db: NaN, then the plan applied, stores,
+    rep_stores [entries of the compact buffer], segs [segments][2]: first destination entry, source index - destination,
+    items [work items][4], dict)."""
+    lib = load_library()
+    nodes, lids, rowptr, colind = _np(nodes, np.float64), _np(lids, np.int32), _np(rowptr, np.int32), _np(colind, np.int32)
+    khat, factors = _np(khat, np.float64), _np(factors, np.float64)
+    fx = None if fixed is None else _np(fixed, np.uint8)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    nsym = khat.shape[0] - 1
+    nnz = len(colind)
+    full, db = np.full(nnz, np.nan), np.full(nnz, np.nan)
+    stores, rep_stores = np.zeros(nnz + 4096, np.int32), np.zeros(nnz, np.int32)
+    segs, items = np.zeros((nnz + 16, 2), np.int32), np.zeros((nnz // 16 + 16, 4), np.int32)
+    counts = (C.c_int * 9)()
+    f = lib.mha_test_block_pattern_step_plan
+    f.argtypes = ([C.c_int] * 6 + [C.c_void_p] * 7 + [C.c_double, C.c_double] + [C.c_int] * 3 + [C.c_void_p] * 3 +
+                  [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p])
+    _check(f(int(dim), int(nrows), lids.shape[0], nodes.shape[1], lids.shape[1], nsym, vp(nodes), vp(lids), vp(rowptr),
+             vp(colind), vp(fx), vp(khat), vp(factors), float(scale_u), float(scale_t), int(chunk_elems), int(num_cus),
+             int(max_patterns), vp(full), vp(db), vp(stores), len(stores), vp(rep_stores), len(rep_stores), vp(segs),
+             segs.size, vp(items), items.size, counts))
+    info = dict(zip(("items", "segments", "max_item_segments", "span_entries", "segment_registers", "runs", "roles",
+                     "rep_entries", "rep_items"), counts))
+    return (full, db, stores, rep_stores[:info["rep_entries"]], segs[:info["segments"]], items[:info["items"]], info)
+
+
 def row_partition(dim, nodes, lids, nrows, rowptr, caps=None):
     """Host-only: the row-owner partition (mha_row_partition_*).  -> dict(row_ptr, rows, elem_ptr, elems, max_*)."""
     lib = load_library()

@@ -365,7 +365,7 @@ bool AssemblyManager::porousDatabaseUsable() {
 
 void AssemblyManager::launchDatabaseCopy(double *crs_vals) {
   launch_line_copy(porous_db_.copy_items.data(), porous_db_.num_items, porous_db_.copy_segs.data(), porous_db_.num_segs,
-                   h_rowptr_[nrows_], crs_vals, stream_);
+                   h_rowptr_[nrows_], crs_vals, crs_vals, stream_);
 }
 
 // The direct form of the porousMixed assembly (kernels/porous_element.hip) rests on one property of the mesh: any two
@@ -2136,6 +2136,7 @@ void AssemblyManager::prepareBlockPattern() {
   BlockPatternData &bp = bpat_;
   bp.tried = true;
   bp.usable = false;
+  ++bpat_generation_;  // whatever is rebuilt below, kept representatives were made from the tables before it
   const char *mode = std::getenv("MHA_K2");
   if (mode && std::string(mode) == "blocks") { bp.why = "row-block kernel requested (MHA_K2=blocks)"; return; }
   if (ro_.num_general_blocks > 0) { bp.why = "block has non-affine elements"; return; }
@@ -2219,19 +2220,30 @@ void AssemblyManager::prepareBlockPattern() {
   // Geometry-database mode (reference: identifyVolumetricDatabase, assemblyManager.cpp:4314-4467,
   // here with exact matching): with ONE geometry shape in the block the rows of a row block depend on its pattern
   // only -- the representatives (every unit of one block per role, the role's first; block_pattern_reps_kernel) are
-  // computed and their runs replicated.  MHA_BP_DATABASE=0 keeps the full kernel.
+  // computed into a buffer of their own, rep_vals, and every CRS entry is copied from there.  The representatives do
+  // not depend on the solution, so launchRowOwner keeps them until their inputs change (MHA_BP_REP_CACHE=0: computed
+  // every call).  MHA_BP_DATABASE=0 keeps the full kernel, as does a graph with CRS entries that no row block owns (the copy would have nothing to put there).
   bp.db_mode = false;
   const char *dbm = std::getenv("MHA_BP_DATABASE");
   if (ro_.num_shapes == 1 && !(dbm && dbm[0] == '0')) {
-    const BpRepPlan rp = build_rep_plan(h);
-    const CopyPlan cp = build_copy_plan(block_pattern_copy_runs(h), d.nnz);
+    BpRepPlan rp = build_rep_plan(h);
+    const BpRepMap map = build_rep_map(h);
+    std::vector<CopyRun> runs = block_pattern_rep_copy_runs(h, map);
+    int64_t covered = 0;
+    for (const CopyRun &r : runs) covered += r.len;
+    if (map.size == 0 || covered != d.nnz) return;  // (runs never overlap: every row has one owner)
+    compact_rep_plan(rp, map);
+    const CopyPlan cp = build_copy_plan_from(std::move(runs), d.nnz, map.size);
     bp.rep_items.upload(rp.item);
     bp.rep_lanes.upload(rp.lane);
     bp.rep_num_items = rp.num_items();
+    bp.rep_vals.resize(static_cast<size_t>(map.size));
     bp.copy_items.upload(cp.item);
     bp.copy_segs.upload(cp.seg);
     bp.copy_num_items = cp.num_items();
     bp.copy_num_segs = cp.num_segs();
+    const char *keep = std::getenv("MHA_BP_REP_CACHE");  // cross-check knob: 0 recomputes the representatives every call
+    bp.keep_reps = !(keep && keep[0] == '0');
     bp.db_mode = true;
   }
 }
@@ -2441,12 +2453,24 @@ void AssemblyManager::launchRowOwner(bool compute_jacobian, bool overwrite, doub
   if (overwrite) MHA_HIP(hipMemsetAsync(res, 0, sizeof(double) * nrows_, side_stream_));
   // K2: pattern GEMMs on the matrix cores when the rows group, row blocks otherwise
   if (bpat_.usable && bpat_.db_mode && out.overwrite && (reinterpret_cast<uintptr_t>(out.vals) & 127u) == 0) {  // (the copy's chunks sit on 128-byte lines of the caller's array)
-    // geometry-database mode: the representatives' rows, then their copies (same stream: ordered)
-    launch_block_pattern_reps(bpat_.rep_items.data(), bpat_.rep_lanes.data(), bpat_.rep_num_items, bpat_.erec2.data(),
-                              bpat_.w.data(), out.vals, su, st, stream_);
-    // (lines that mix copied and representative entries are stored whole: the representatives' lanes store back the
-    // bits they read, which the kernel above wrote earlier on this stream; no other wavefront writes those lines)
-    launch_line_copy(bpat_.copy_items.data(), bpat_.copy_num_items, bpat_.copy_segs.data(), bpat_.copy_num_segs, h_rowptr_[nrows_], out.vals, stream_);
+    // geometry-database mode: the representatives into rep_vals when their inputs changed -- the element records and
+    // W images (the mesh, the graph: prepareBlockPattern's generation), the two scales (coefficients, time-integration
+    // weights), the stream that orders rep_vals' writer before its readers -- then every CRS entry copied from there
+    RepKey key;
+    std::memcpy(&key.su, &su, sizeof(su));
+    std::memcpy(&key.st, &st, sizeof(st));
+    key.generation = bpat_generation_;
+    key.stream = stream_;
+    if (!bpat_.keep_reps || !bpat_.rep_key_valid || !(key == bpat_.rep_key)) {
+      bpat_.rep_key_valid = false;  // (stays so if the launch throws)
+      launch_block_pattern_reps(bpat_.rep_items.data(), bpat_.rep_lanes.data(), bpat_.rep_num_items, bpat_.erec2.data(),
+                                bpat_.w.data(), bpat_.rep_vals.data(), su, st, stream_);
+      bpat_.rep_key = key;
+      bpat_.rep_key_valid = true;
+      ++rep_launches_;
+    }
+    launch_line_copy(bpat_.copy_items.data(), bpat_.copy_num_items, bpat_.copy_segs.data(), bpat_.copy_num_segs, h_rowptr_[nrows_],
+                     bpat_.rep_vals.data(), out.vals, stream_);
     last_db_mode_ = 1;
   } else if (bpat_.usable) {
     last_db_mode_ = 0;
@@ -2474,6 +2498,7 @@ int64_t AssemblyManager::info(const std::string &key) const {
   if (key == "num_ip") return nq_;
   if (key == "last_path") return last_path_;
   if (key == "jacobian_database_mode") return last_db_mode_;  // the last affine row-owner Jacobian replicated one block per pattern
+  if (key == "block_pattern_rep_launches") return rep_launches_;  // representative launches of the geometry-database mode so far
   if (key == "affine_shapes") return ro_.ready ? ro_.k1_plan.num_shapes : 0;  // distinct geometry records behind the residual kernel's database index
   if (key == "porous_direct") return last_porous_direct_;  // the last row-gather assembly of a porousMixed block stored straight into the CRS
   if (key == "workset_size") return wkset_.maxElem;

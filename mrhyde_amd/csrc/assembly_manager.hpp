@@ -241,6 +241,13 @@ class AssemblyManager {
   RowBlocksDev generalRowBlocksDev() const;
   void launchGeneralRowOwner(bool compute_jacobian, bool overwrite, double *res, double *crs_vals, bool ordered = false);
   // row blocks keyed by assembly pattern: the matrix-core form of K2 (block_pattern.hpp); !usable -> the row-block kernel
+  // inputs of the geometry-database representatives: the bits of su = alpha_u * kappa and st = alpha_t * rho * c_p,
+  // the generation of the tables, the stream rep_vals was written on
+  struct RepKey {
+    uint64_t su = 0, st = 0, generation = 0;
+    hipStream_t stream = nullptr;
+    bool operator==(const RepKey &o) const { return su == o.su && st == o.st && generation == o.generation && stream == o.stream; }
+  };
   struct BlockPatternData {
     bool tried = false, usable = false;
     std::string why;
@@ -252,9 +259,15 @@ class AssemblyManager {
     // geometry-database mode (one shape in the block): the kernel on one representative block per role + replication
     bool db_mode = false;
     DeviceBuffer<int32_t> rep_items, rep_lanes;  // the representatives, one wavefront per item (BpRepPlan)
-    DeviceBuffer<int32_t> copy_items, copy_segs;  // the copy plan: copy_plan.hpp
+    DeviceBuffer<double> rep_vals;  // the representatives' CRS entries, compact (BpRepMap), kept across assemblies
+    DeviceBuffer<int32_t> copy_items, copy_segs;  // the copy plan, every CRS entry from rep_vals: copy_plan.hpp
     int rep_num_items = 0, copy_num_items = 0, copy_num_segs = 0;
+    RepKey rep_key;  // what rep_vals was computed from
+    bool rep_key_valid = false;
+    bool keep_reps = true;  // MHA_BP_REP_CACHE != 0
   } bpat_;
+  uint64_t bpat_generation_ = 0;  // bumped whenever prepareBlockPattern rebuilds erec2, w or the plans
+  int64_t rep_launches_ = 0;
   void prepareBlockPattern();
 
   std::vector<int32_t> db_index_, db_first_users_;  // basis database: representative of every element, their element ids

@@ -727,4 +727,65 @@ void rep_plan_host_apply(const BlockPatternPlan &pl, const BpRepPlan &rp, const 
   }
 }
 
+BpRepMap build_rep_map(const BlockPatternPlan &pl) {
+  struct Run { int64_t crs, rep, len; };
+  std::vector<Run> runs;
+  BpRepMap m;
+  for (int k = 0; k < pl.num_roles; ++k) {
+    const int32_t *ro = &pl.role[static_cast<size_t>(k) * kBpRoleInts];
+    if (ro[R_NBLOCKS] < 1) continue;
+    const int64_t row_base = (static_cast<int64_t>(ro[R_ROWB_HI]) << 32) | static_cast<uint32_t>(ro[R_ROWB_LO]);
+    const int32_t *rl = &pl.runlen[static_cast<size_t>(pl.role_runlen_off[k])];
+    for (int r = 0; r < ro[R_NRUNS]; ++r) {
+      runs.push_back({pl.rowbase[static_cast<size_t>(row_base + r)], m.size, rl[r]});
+      m.size += rl[r];
+    }
+  }
+  std::sort(runs.begin(), runs.end(), [](const Run &a, const Run &b) { return a.crs < b.crs; });
+  for (size_t i = 0; i < runs.size(); ++i) {
+    MHA_REQUIRE(i == 0 || runs[i - 1].crs + runs[i - 1].len <= runs[i].crs, MHA_ERR_STATE, "representatives: two roles' first blocks share CRS entries");
+    m.crs.push_back(runs[i].crs);
+    m.rep.push_back(runs[i].rep);
+    m.len.push_back(runs[i].len);
+  }
+  return m;
+}
+
+int64_t BpRepMap::index(int64_t e) const {
+  const size_t i = static_cast<size_t>(std::upper_bound(crs.begin(), crs.end(), e) - crs.begin());
+  if (i == 0 || e >= crs[i - 1] + len[i - 1]) return -1;
+  return rep[i - 1] + (e - crs[i - 1]);
+}
+
+void compact_rep_plan(BpRepPlan &rp, const BpRepMap &m) {
+  for (int i = 0; i < rp.num_items(); ++i) {
+    int32_t *R = rp.lane.data() + static_cast<size_t>(i) * kBpRepLaneRows * 64;
+    for (int t = 0; t < 4; ++t)
+      for (int lane = 0; lane < 64; ++lane) {
+        int32_t &d = R[(16 + t) * 64 + lane];
+        if (d < 0) continue;
+        const int64_t c = m.index(d);
+        MHA_REQUIRE(c >= 0 && c < m.size, MHA_ERR_STATE, "representatives: an item stores outside the first blocks' rows");
+        d = static_cast<int32_t>(c);
+      }
+  }
+}
+
+std::vector<CopyRun> block_pattern_rep_copy_runs(const BlockPatternPlan &pl, const BpRepMap &m) {
+  std::vector<CopyRun> runs;
+  for (int k = 0; k < pl.num_roles; ++k) {
+    const int32_t *ro = &pl.role[static_cast<size_t>(k) * kBpRoleInts];
+    const int64_t row_base = (static_cast<int64_t>(ro[R_ROWB_HI]) << 32) | static_cast<uint32_t>(ro[R_ROWB_LO]);
+    const int nruns = ro[R_NRUNS], nblocks = ro[R_NBLOCKS];
+    const int32_t *rl = &pl.runlen[static_cast<size_t>(pl.role_runlen_off[k])];
+    for (int r = 0; r < nruns && nblocks > 0; ++r) {
+      const int64_t src = m.index(pl.rowbase[static_cast<size_t>(row_base + r)]);
+      MHA_REQUIRE(src >= 0, MHA_ERR_STATE, "representatives: a run of a first block is not in the map");
+      for (int j = 0; j < nblocks; ++j)
+        runs.push_back({src, pl.rowbase[static_cast<size_t>(row_base + static_cast<int64_t>(j) * nruns + r)], rl[r]});
+    }
+  }
+  return runs;
+}
+
 }  // namespace mha

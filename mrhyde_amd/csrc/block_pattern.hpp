@@ -109,4 +109,20 @@ BpRepPlan build_rep_plan(const BlockPatternPlan &plan);
 void rep_plan_host_apply(const BlockPatternPlan &plan, const BpRepPlan &rep, const double *factors, double su, double st,
                          double *vals, int32_t *stores);
 
+// The representatives' own buffer (rep_vals): the geometry-database mode keeps them from one assembly to the next --
+// their inputs (element records, W images, the two scales) do not depend on the solution -- in a compact buffer that
+// holds the runs of consecutive rows of every role's first block back to back, role by role.  The map below takes a
+// CRS entry of a representative to its index there; from it follow the kernel's item table (compact_rep_plan: the
+// four result registers of every lane address rep_vals) and the copy's runs, which source EVERY entry of the CRS
+// array, the representatives' own positions included, from rep_vals (copy_plan.hpp, separate source).
+struct BpRepMap {
+  std::vector<int64_t> crs, rep, len;  // runs sorted by CRS entry: first CRS entry, first rep_vals index, entries
+  int64_t size = 0;                    // entries of rep_vals
+  int64_t index(int64_t crs_entry) const;  // -1: not a representative's entry
+};
+BpRepMap build_rep_map(const BlockPatternPlan &plan);
+void compact_rep_plan(BpRepPlan &rep, const BpRepMap &map);
+// (rep_vals index, CRS entry, length) for every run of every block of every role, the first blocks included
+std::vector<CopyRun> block_pattern_rep_copy_runs(const BlockPatternPlan &plan, const BpRepMap &map);
+
 }  // namespace mha

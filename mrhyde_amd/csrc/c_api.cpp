@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <string>
 
@@ -834,6 +835,44 @@ int mha_test_block_pattern_rep_plan(int dim, int num_rows, int num_elems, int nn
     counts[1] = pl.num_roles;
     counts[2] = pl.num_parts;
     counts[3] = static_cast<int>(runs.size());
+  });
+}
+
+// The geometry-database step with kept representatives on the host: the representatives' items walked into their own
+// compact buffer (BpRepMap, compact_rep_plan), then the separate-source copy plan applied to vals_db.
+int mha_test_block_pattern_step_plan(int dim, int num_rows, int num_elems, int nnodes, int n, int nsym,
+                                     const double *nodes, const int32_t *lids, const int32_t *rowptr,
+                                     const int32_t *colind, const uint8_t *fixed, const double *khat,
+                                     const double *factors, double scale_u, double scale_t, int chunk_elems, int num_cus,
+                                     int max_patterns, double *vals_full, double *vals_db, int32_t *stores,
+                                     int64_t stores_len, int32_t *rep_stores, int64_t rep_stores_len, int32_t *segs,
+                                     int64_t segs_len, int32_t *items, int64_t items_len, int *counts) {
+  return guarded([&] {
+    MHA_REQUIRE(factors && vals_full && vals_db && stores && rep_stores && segs && items && counts, MHA_ERR_INVALID, "null argument");
+    const mha::BlockPatternPlan pl = test_block_patterns(dim, num_rows, num_elems, nnodes, n, nsym, nodes, lids, rowptr,
+                                                         colind, fixed, khat, chunk_elems, num_cus, max_patterns);
+    const int64_t nnz = rowptr[num_rows];
+    mha::block_patterns_host_apply(pl, factors, scale_u, scale_t, true, vals_full);
+    mha::BpRepPlan rp = mha::build_rep_plan(pl);
+    const mha::BpRepMap map = mha::build_rep_map(pl);
+    mha::compact_rep_plan(rp, map);
+    MHA_REQUIRE(rep_stores_len >= map.size, MHA_ERR_INVALID, "representative store counters too short");
+    std::vector<double> rep_vals(static_cast<size_t>(map.size), std::numeric_limits<double>::quiet_NaN());
+    mha::rep_plan_host_apply(pl, rp, factors, scale_u, scale_t, rep_vals.data(), rep_stores);
+    std::vector<mha::CopyRun> runs = mha::block_pattern_rep_copy_runs(pl, map);
+    const int num_runs = static_cast<int>(runs.size());
+    const mha::CopyPlan cp = mha::build_copy_plan_from(std::move(runs), nnz, map.size);
+    MHA_REQUIRE(stores_len >= (nnz + mha::kCopySpanEntries - 1) / mha::kCopySpanEntries * mha::kCopySpanEntries,
+                MHA_ERR_INVALID, "store counters must cover whole spans");
+    copy_plan_counts(cp, counts);
+    counts[5] = num_runs;
+    counts[6] = pl.num_roles;
+    counts[7] = static_cast<int>(map.size);
+    counts[8] = rp.num_items();
+    MHA_REQUIRE(segs_len >= 2ll * counts[1] && items_len >= 4ll * counts[0], MHA_ERR_INVALID, "output arrays too short");
+    std::copy(cp.seg.begin(), cp.seg.begin() + 2 * counts[1], segs);
+    std::copy(cp.item.begin(), cp.item.end(), items);
+    mha::copy_plan_host_apply(cp, vals_db, stores, rep_vals.data());
   });
 }
 

@@ -10,6 +10,11 @@
 // A lane finds its source through the SEGMENTS: a destination-sorted list that tiles [0, nnz) without gaps,
 // {first entry, source - destination}, in-place stretches with offset 0, neighbours with equal offsets merged.  In-place
 // lanes of a kept span read back their own entry and store the same bits.  Entries at or past nnz are never stored.
+//
+// A plan with a SEPARATE SOURCE (build_copy_plan_from; the thermal geometry database, whose representatives live in a
+// compact buffer of their own that is kept from one assembly to the next) has no in-place entries: its runs tile
+// [0, nnz), a segment's offset is (entry of the source buffer) - (destination entry), offset 0 is an offset like any
+// other, and every span is a work item.  The caller's array is written only.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -28,6 +33,7 @@ struct CopyRun {
 
 struct CopyPlan {
   int64_t nnz = 0;
+  int64_t nsrc = 0;           // entries of the separate source buffer; 0: the plan copies inside vals
   std::vector<int32_t> seg;   // [num_segs][2]: first destination entry, source - destination; the last
                               // kCopySegRegs records are sentinels {INT32_MAX, 0}
   std::vector<int32_t> item;  // [num_items][4]: first line of the span, its first segment, segments it meets, 0
@@ -41,8 +47,13 @@ struct CopyPlan {
 // entries (a run's source is never another run's destination).  Throws MHA_ERR_INVALID otherwise.
 CopyPlan build_copy_plan(std::vector<CopyRun> runs, int64_t nnz);
 
+// Separate source: runs (entry of src[0, nsrc), destination entry, length) whose destinations tile [0, nnz) exactly.
+CopyPlan build_copy_plan_from(std::vector<CopyRun> runs, int64_t nnz, int64_t nsrc);
+
 // The kernel's lane logic on the host, work item by work item (every load of an item before its first store).
 // stores: optional counters [nnz rounded up to whole spans], incremented for every entry a lane stores.
-void copy_plan_host_apply(const CopyPlan &plan, double *vals, int32_t *stores);
+// src: the source buffer of a separate-source plan (every load is checked against [0, nsrc)); nullptr for a plan that
+// copies inside vals.
+void copy_plan_host_apply(const CopyPlan &plan, double *vals, int32_t *stores, const double *src = nullptr);
 
 }  // namespace mha

@@ -81,10 +81,11 @@ void launch_block_pattern_jacobian(const BlockPatternDev &d, const RowOut &out, 
 // the geometry-database mode's representatives, one wavefront per item of the BpRepPlan (block_pattern.hpp)
 void launch_block_pattern_reps(const int32_t *items, const int32_t *lanes, int nitems, const double *erec2, const double *w,
                                double *vals, double su, double st, hipStream_t stream);
-// line_copy.hip: the database modes' copy of representative entries inside vals in whole 128-byte lines
-// (copy_plan.hpp: items [n][4], segments [nseg][2]); vals must start on a 128-byte line
-void launch_line_copy(const int32_t *items, int nitems, const int32_t *seg, int nseg, int64_t nnz, double *vals,
-                      hipStream_t stream);
+// line_copy.hip: the database modes' copy of representative entries into vals in whole 128-byte lines
+// (copy_plan.hpp: items [n][4], segments [nseg][2]); vals must start on a 128-byte line.  src: vals itself (a plan
+// that copies inside vals) or the separate source buffer of a build_copy_plan_from plan
+void launch_line_copy(const int32_t *items, int nitems, const int32_t *seg, int nseg, int64_t nnz, const double *src,
+                      double *vals, hipStream_t stream);
 void launch_build_erec(int dim, const RowBlocksDev &rb, const double *geo, double *erec, int total,
                        hipStream_t stream);
 // K1: element-wise residual (-> res with atomics)

@@ -6,7 +6,8 @@
 // except past nnz.  Each lane takes the offset of the last segment that starts at or before each of its two entries:
 // the item's segment records are loaded wave-uniform (scalar loads), kCopySegRegs at a time, and compared per lane.
 // The sources are the representatives' entries (a few MB, L2-resident) at any entry offset: 8-byte loads, all of a
-// span's issued before its first store.
+// span's issued before its first store.  SEP: the sources sit in a buffer of their own (the thermal geometry database's
+// kept representatives, copy_plan.hpp) and vals is written only; otherwise they are entries of vals itself.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -18,10 +19,11 @@ namespace mha {
 
 namespace {
 
-template <int U, int R>
+template <int U, int R, bool SEP>
 __global__ __launch_bounds__(256) void line_copy_kernel(const int4 *__restrict__ items, int nitems,
                                                         const int2 *__restrict__ seg, int nnz,
-                                                        double *vals) {
+                                                        const double *sep_src, double *vals) {
+  const double *src = SEP ? sep_src : vals;
   const int lane = threadIdx.x & 63;
   const int wave0 = __builtin_amdgcn_readfirstlane((blockIdx.x * 256 + threadIdx.x) >> 6), nwaves = (gridDim.x * 256) >> 6;
   for (int w = wave0; w < nitems; w += nwaves) {
@@ -51,8 +53,8 @@ __global__ __launch_bounds__(256) void line_copy_kernel(const int4 *__restrict__
 #pragma unroll
     for (int u = 0; u < U; ++u) {  // lanes past nnz load an entry that exists and store nothing
       const int e = s0 + u * kCopyWaveEntries + 2 * lane;
-      x0[u] = vals[e < nnz ? e + off0[u] : 0];
-      x1[u] = vals[e + 1 < nnz ? e + 1 + off1[u] : 0];
+      x0[u] = src[e < nnz ? e + off0[u] : 0];
+      x1[u] = src[e + 1 < nnz ? e + 1 + off1[u] : 0];
     }
     typedef double v2d_t __attribute__((ext_vector_type(2)));
     if (s0 + kCopySpanEntries <= nnz) {  // wave-uniform: every span but the last
@@ -78,17 +80,22 @@ __global__ __launch_bounds__(256) void line_copy_kernel(const int4 *__restrict__
 
 }  // namespace
 
-void launch_line_copy(const int32_t *items, int nitems, const int32_t *seg, int nseg, int64_t nnz, double *vals,
-                      hipStream_t stream) {
+void launch_line_copy(const int32_t *items, int nitems, const int32_t *seg, int nseg, int64_t nnz, const double *src,
+                      double *vals, hipStream_t stream) {
   if (nitems <= 0) return;
   MHA_REQUIRE((reinterpret_cast<uintptr_t>(vals) & 127u) == 0, MHA_ERR_INVALID, "database mode: CRS values must start on a 128-byte line");
   constexpr int U = kCopySpanEntries / kCopyWaveEntries;
   static_assert(U * kCopyWaveEntries == kCopySpanEntries, "a span is whole store instructions of a wavefront");
   // one work item per wavefront: capping the grid (2048 / 8192 workgroups walking the items grid-stride) was slower
   const int grid = (nitems + 3) / 4;
-  hipLaunchKernelGGL((line_copy_kernel<U, kCopySegRegs>), dim3(grid), dim3(256), 0, stream,
-                     reinterpret_cast<const int4 *>(items), nitems, reinterpret_cast<const int2 *>(seg),
-                     static_cast<int>(nnz), vals);
+  if (src != vals)
+    hipLaunchKernelGGL((line_copy_kernel<U, kCopySegRegs, true>), dim3(grid), dim3(256), 0, stream,
+                       reinterpret_cast<const int4 *>(items), nitems, reinterpret_cast<const int2 *>(seg),
+                       static_cast<int>(nnz), src, vals);
+  else
+    hipLaunchKernelGGL((line_copy_kernel<U, kCopySegRegs, false>), dim3(grid), dim3(256), 0, stream,
+                       reinterpret_cast<const int4 *>(items), nitems, reinterpret_cast<const int2 *>(seg),
+                       static_cast<int>(nnz), src, vals);
   MHA_HIP(hipGetLastError());
 }
 

@@ -53,6 +53,22 @@ int mha_test_block_pattern_rep_plan(int dim, int num_rows, int num_elems, int nn
                                     int32_t *units, int64_t units_len, int32_t *part_tiles, int64_t part_tiles_len,
                                     int *counts);
 
+/* The geometry-database step with kept representatives on the host (block_pattern.hpp, BpRepMap): the representatives'
+ * items store into a compact buffer of their own (rep_stores [>= its entries]: incremented per stored entry) and the
+ * separate-source copy plan (copy_plan.hpp, build_copy_plan_from) writes EVERY entry of vals_db (caller-filled, e.g.
+ * NaN) from that buffer; every load of the copy is checked against the buffer (an error otherwise).  vals_full, stores:
+ * as mha_test_block_pattern_copy_plan.  segs [segs_len >= 2 x segments]: first destination entry, source index -
+ * destination entry; items [items_len >= 4 x work items]: first line, first segment, segments met, 0.
+ * counts[9] = the five of mha_test_copy_plan_host_apply, copy runs, roles, entries of the compact buffer, items of the
+ * representatives' plan. */
+int mha_test_block_pattern_step_plan(int dim, int num_rows, int num_elems, int nnodes, int n, int nsym,
+                                     const double *nodes, const int32_t *lids, const int32_t *rowptr,
+                                     const int32_t *colind, const uint8_t *fixed, const double *khat,
+                                     const double *factors, double scale_u, double scale_t, int chunk_elems, int num_cus,
+                                     int max_patterns, double *vals_full, double *vals_db, int32_t *stores,
+                                     int64_t stores_len, int32_t *rep_stores, int64_t rep_stores_len, int32_t *segs,
+                                     int64_t segs_len, int32_t *items, int64_t items_len, int *counts);
+
 #ifdef __cplusplus
 }
 #endif
