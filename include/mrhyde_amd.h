@@ -536,6 +536,49 @@ int mha_swhdg_subgrid_solve(mha_context *ctx, double *u_dev, const double *u_pre
 int mha_swhdg_condensed_element(mha_context *ctx, const double *u_dev, const double *u_prev_dev, const double *u_stage_dev,
                                 const double *lambda_dev, const uint8_t *side_types_dev, const double *farfield_host,
                                 double *schur_dev, double *gvec_dev, double *du_dev, int32_t *num_singular_dev);
+/* ---- HDG subgrids of m x m sub-elements per macro element -------------------------------------------------------
+ * The DtN subgrid model refines the macro element (SubGridDtN_Solver::assembleJacobianResidual,
+ * src/subgrid/subgridDtN_solver.cpp:681-903); one HDG element per subgrid (the entry points above) is its degenerate case.
+ * Scope: 2-D quads, H / Hux / Huy HGRAD order 1 and continuous inside a macro element, the macro trace HFACE degree 1 (24
+ * unknowns, as above), m in 1..4: n_int = 3 (m+1)^2 = 12, 27, 48, 75 interior unknowns per macro element.
+ * mha_swhdg_set_subgrids declares that elements [k m^2, (k+1) m^2) of the block are macro element k's structured sub-mesh,
+ * row-major with x fastest, and validates on the host that the LIDs of macro element k are shared only inside k with the Q1
+ * connectivity of an m x m grid, and that the sub-mesh vertices are the bilinear image of the uniform m x m subdivision of
+ * the macro quad to 1e-12 x its size.  m = 0 clears the layout; m > 4 is refused (MHA_ERR_INVALID: the dense interior
+ * solve holds at most 75 unknowns on the chip); mha_set_mesh clears it.  With no layout set every other entry point behaves
+ * exactly as before.
+ * Semantics: volumeResidual (src/physics/shallowwaterHybridized.cpp:113-184) on every sub-element, summed into the interior
+ * rows through the sub-mesh LIDs (subgridDtN_solver.cpp:774-808); boundaryResidual (:190-263) on the 4m sub-sides on the
+ * macro boundary only; the trace state at a sub-side point is the macro edge's HFACE basis there
+ * (src/subgrid/subgridDtN.cpp:746-870, auxside_basis): sub-side j of m on a macro edge covers the edge coordinate
+ * [-1 + 2j/m, -1 + 2(j+1)/m], edges oriented as mha_swhdg_element_blocks documents; trace rows: computeFlux (:270-368)
+ * against that macro trace basis over the sub-sides of each macro edge (updateFlux, subgridDtN_solver.cpp:1542-1616).
+ * Interior unknowns of a macro element are flattened (variable, sub-mesh node), node = ay (m+1) + ax; for m = 1 that is
+ * the (variable, dof) order of mha_swhdg_condensed_element.  lambda_dev[Em][24], side_types_dev[Em][4] (per MACRO side).
+ * mha_swhdg_condensed_subgrid: assembly + static condensation in one kernel, one workgroup per macro element, the
+ * [n_int + 24] x [n_int + 24 + 1] system in LDS, a dense Gauss-Jordan solve with partial pivoting there (the reference
+ * uses a sparse direct solver; at these sizes the dense solve is the one that never leaves the chip), the A_lu A_uu^-1 A_ul
+ * product on the fp64 matrix cores.  Outputs as mha_batched_condense defines them: schur_dev[Em][24][24], gvec_dev[Em][24],
+ * du_dev[Em][n_int]; any may be NULL, not all; *num_singular_dev += singular interior blocks.  Contributions are summed
+ * in a fixed order: two runs are bit-identical.  Deck-string sources are refused.  No synchronisation, no allocation.
+ * mha_swhdg_subgrid_solve on a block with a layout runs this kernel per pass: the same protocol with norms and du over the
+ * n_int unknowns of a macro element, iters / resnorm / schur / gvec per macro element, workspace bytes following the layout.
+ * mha_swhdg_subgrid_blocks: the UNCONDENSED res_dev[Em][n_int+24] = -res.val() and blocks_dev[Em][n_int+24][n_int+24] (either
+ * may be NULL), by a plain unfused kernel: the independent implementation the fused kernel is compared with.
+ * The condensed blocks feed mha_scatter_plan_* with the macro trace LIDs, unchanged.                                   */
+int mha_swhdg_set_subgrids(mha_context *ctx, int m);
+int mha_swhdg_condensed_subgrid(mha_context *ctx, const double *u_dev, const double *u_prev_dev, const double *u_stage_dev,
+                                const double *lambda_dev, const uint8_t *side_types_dev, const double *farfield_host,
+                                double *schur_dev, double *gvec_dev, double *du_dev, int32_t *num_singular_dev);
+int mha_swhdg_subgrid_blocks(mha_context *ctx, const double *u_dev, const double *u_prev_dev, const double *u_stage_dev,
+                             const double *lambda_dev, const uint8_t *side_types_dev, const double *farfield_host,
+                             double *res_dev, double *blocks_dev);
+/* Mesh helper (input generation): ncell_macro[2] macro quads on [lo, hi], each an m x m sub-mesh.  sizes: nelem = Em m^2,
+ * ndof = Em n_int, ntrace = rows of the macro trace system.  nodes[nelem][4][2], lids[nelem][12], offsets[12] for
+ * mha_set_mesh; trace_lids[Em][24] for mha_scatter_plan_create.                                                          */
+int mha_mesh_swhdg_subgrids_sizes(const int *ncell_macro, int m, int *nelem, int64_t *ndof, int64_t *ntrace);
+int mha_mesh_swhdg_subgrids(const int *ncell_macro, int m, const double *lo, const double *hi, double *nodes,
+                            int32_t *lids, int32_t *offsets, int32_t *trace_lids);
 /* Batched static condensation of element blocks: eliminates the n_int interior unknowns of every element.
  * replaces: the element-local direct solve of the subgrid solver and its forward sensitivities d u / d lambda
  * (SubGridDtN_Solver, src/subgrid/subgridDtN_solver.cpp:681-903, 1542-1616) in Schur-complement form.

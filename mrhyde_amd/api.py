@@ -30,7 +30,8 @@ EXPORTS = [
     "mha_sparse3d_create", "mha_sparse3d_views", "mha_sparse3d_size", "mha_sparse3d_destroy", "mha_database_build",
     "mha_database_get", "mha_apply_mass_matrix_free", "mha_swhdg_subgrid_workspace_bytes", "mha_swhdg_subgrid_solve",
     "mha_set_element_data", "mha_import_mesh_data", "mha_set_parameter_vector", "mha_closest_points", "mha_kl_expansion",
-    "mha_kl_indices",
+    "mha_kl_indices", "mha_swhdg_set_subgrids", "mha_swhdg_condensed_subgrid", "mha_swhdg_subgrid_blocks",
+    "mha_mesh_swhdg_subgrids_sizes", "mha_mesh_swhdg_subgrids",
 ]
 KL_MAX_TERMS = 8  # MHA_KL_MAX_TERMS: KL roots per direction the kernels evaluate
 MASS_ON_THE_FLY, MASS_LOCAL, MASS_DATABASE, MASS_DATABASE_SPARSE = 0, 1, 2, 3
@@ -138,6 +139,11 @@ def load_library():
         _lib.mha_closest_points.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _lib.mha_kl_expansion.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
         _lib.mha_kl_indices.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        _lib.mha_swhdg_set_subgrids.argtypes = [C.c_void_p, C.c_int]
+        _lib.mha_swhdg_condensed_subgrid.argtypes = [C.c_void_p] * 11
+        _lib.mha_swhdg_subgrid_blocks.argtypes = [C.c_void_p] * 9
+        _lib.mha_mesh_swhdg_subgrids_sizes.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        _lib.mha_mesh_swhdg_subgrids.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
     return _lib
 
 
@@ -446,6 +452,36 @@ def mesh_multi(dim, ncell, types, orders, lo=None, hi=None):
     return m
 
 
+def mesh_swhdg_subgrids(ncell_macro, m, lo=None, hi=None):
+    """HDG subgrid mesh of shallowwaterHybridized (mha_mesh_swhdg_subgrids): ncell_macro macro quads, each an m x m sub-mesh
+    whose elements are consecutive (row-major, x fastest).  -> dict(nodes [E][4][2], lids [E][12], offsets [12], trace_lids
+    [Em][24], nelem, nmacro, ndof, ntrace, n_int, m)."""
+    lib = load_library()
+    nc = _np(ncell_macro, np.int32)
+    lo = _np(np.zeros(2) if lo is None else lo, np.float64)
+    hi = _np(np.ones(2) if hi is None else hi, np.float64)
+    ne, nd, nt = C.c_int(), C.c_int64(), C.c_int64()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(lib.mha_mesh_swhdg_subgrids_sizes(vp(nc), int(m), C.byref(ne), C.byref(nd), C.byref(nt)))
+    nm = int(nc[0]) * int(nc[1])
+    out = dict(nodes=np.zeros((ne.value, 4, 2)), lids=np.zeros((ne.value, 12), np.int32), offsets=np.zeros(12, np.int32),
+               trace_lids=np.zeros((nm, 24), np.int32), nelem=ne.value, nmacro=nm, ndof=nd.value, ntrace=nt.value,
+               n_int=3 * (m + 1) ** 2, m=int(m), dim=2)
+    _check(lib.mha_mesh_swhdg_subgrids(vp(nc), int(m), vp(lo), vp(hi), vp(out["nodes"]), vp(out["lids"]), vp(out["offsets"]),
+                                       vp(out["trace_lids"])))
+    return out
+
+
+def check_swhdg_subgrids(m, nodes, lids, offsets, nrows):
+    """Host-only test hook (csrc/test_hooks.h, not part of the boundary): the layout check of Block.set_swhdg_subgrids
+    on host arrays; raises MhaError."""
+    nodes, lids, offsets = _np(nodes, np.float64), _np(lids, np.int32), _np(offsets, np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    f = load_library().mha_test_swhdg_check_subgrids
+    f.argtypes = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3
+    _check(f(int(m), lids.shape[0], int(nrows), vp(nodes), vp(lids), vp(offsets)))
+
+
 def block_patterns_host_apply(dim, nodes, lids, nrows, rowptr, colind, khat, factors, fixed=None, scale_u=1.0,
                               scale_t=1.0, chunk_elems=16, num_cus=8, max_patterns=256):
     """Host-only test hook (csrc/test_hooks.h, not part of the boundary): the block-pattern plan of the matrix-core
@@ -730,10 +766,34 @@ class Block:
                                                None if ff is None else ff.ctypes.data_as(C.c_void_p), _ptr(schur), _ptr(gvec),
                                                _ptr(du), _ptr(num_singular)))
 
+    def set_swhdg_subgrids(self, m):
+        """Declare elements [k m^2, (k+1) m^2) as macro element k's m x m sub-mesh (mha_swhdg_set_subgrids; validated on the
+        host; m = 0 clears the layout)."""
+        _check(load_library().mha_swhdg_set_subgrids(self._h, int(m)))
+        self._subgrid_m = int(m)
+
+    def swhdg_condensed_subgrid(self, u, lam, schur=None, gvec=None, du=None, num_singular=None, side_types=None,
+                                farfield=None, u_prev=None, u_stage=None):
+        """The element step of an HDG subgrid in one kernel (mha_swhdg_condensed_subgrid): fills the given CUDA tensors
+        schur [Em][24][24], gvec [Em][24], du [Em][n_int] per macro element; lam [Em][24], side_types [Em][4]."""
+        ff = None if farfield is None else _np(farfield, np.float64)
+        _check(load_library().mha_swhdg_condensed_subgrid(self._h, _ptr(u), _ptr(u_prev), _ptr(u_stage), _ptr(lam),
+                                                          _ptr(side_types), None if ff is None else ff.ctypes.data_as(C.c_void_p),
+                                                          _ptr(schur), _ptr(gvec), _ptr(du), _ptr(num_singular)))
+
+    def swhdg_subgrid_blocks(self, u, lam, res, blocks, side_types=None, farfield=None, u_prev=None, u_stage=None):
+        """The uncondensed res [Em][n_int+24] and blocks [Em][n_int+24][n_int+24] of an HDG subgrid by the plain kernel
+        (mha_swhdg_subgrid_blocks), the independent implementation the fused step is compared with."""
+        ff = None if farfield is None else _np(farfield, np.float64)
+        _check(load_library().mha_swhdg_subgrid_blocks(self._h, _ptr(u), _ptr(u_prev), _ptr(u_stage), _ptr(lam),
+                                                       _ptr(side_types), None if ff is None else ff.ctypes.data_as(C.c_void_p),
+                                                       _ptr(res), _ptr(blocks)))
+
     def swhdg_subgrid_solve(self, u, lam, max_iter, tol, side_types=None, farfield=None, u_prev=None, u_stage=None,
                             want_condensed=True):
         """SubGridDtN_Solver::nonlinearSolver on the device (u updated in place) -> dict(iters, resnorm, schur, gvec, num_singular).
-        No host synchronisation happens inside the call; the tensors are ready once the stream is."""
+        No host synchronisation happens inside the call; the tensors are ready once the stream is.  On a block with a
+        subgrid layout (set_swhdg_subgrids) lam is [Em][24] and every output is per macro element."""
         import torch
         nb = C.c_int64()
         _check(load_library().mha_swhdg_subgrid_workspace_bytes(self._h, C.byref(nb)))

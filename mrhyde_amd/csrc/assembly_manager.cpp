@@ -126,6 +126,7 @@ void AssemblyManager::setMesh(int nelem, const double *nodes, const int32_t *lid
   else d_fixed_.resize(0);
   has_mesh_ = true;
   subgrid_checked_ = false;
+  subgrid_m_ = 0;
   has_graph_ = false;
   porous_direct_ = -1;
   porous_db_ = PorousDatabase();
@@ -1089,9 +1090,87 @@ void AssemblyManager::swhdgCondensedElement(const double *u, const double *u_pre
   timedEnd();
 }
 
+// Layout of an HDG subgrid: elements [k m^2, (k+1) m^2) are macro element k's structured m x m sub-mesh, row-major with x
+// fastest (kernels/swhdg_subgrid.hpp).  Checked here, once: the interior unknowns of a macro element are shared only
+// inside it, with the Q1 connectivity of an m x m grid, and the sub-mesh vertices are the bilinear image of the uniform
+// subdivision of the macro quad to 1e-12 x its size -- which is what makes the macro edge coordinate of a sub-side point
+// affine in the sub-element's own (src/subgrid/subgridDtN.cpp:746-870 maps the points; here the map is closed-form).
+void AssemblyManager::swhdgSetSubgrids(int m) {
+  if (m == 0) { subgrid_m_ = 0; return; }
+  MHA_REQUIRE(has_mesh_, MHA_ERR_STATE, "no mesh: call mha_set_mesh first");
+  MHA_REQUIRE(dynamic_cast<shallowwaterHybridized *>(physics_.get()) != nullptr && dim_ == 2 && n_ == 12, MHA_ERR_INVALID,
+              "HDG subgrids are built for 2-D shallowwaterHybridized blocks of three order-1 variables");
+  MHA_REQUIRE(m >= 1 && m <= 4, MHA_ERR_INVALID,
+              "HDG subgrids: m = " << m << " sub-elements per direction is outside 1..4 (the dense interior solve holds n_int = 3 (m+1)^2 <= 75 unknowns in LDS)");
+  std::vector<int32_t> offs(n_);
+  d_offsets_.download(offs.data());
+  std::vector<double> nodes(static_cast<size_t>(nelem_) * 8);
+  d_nodes_.download(nodes.data());
+  check_swhdg_subgrids(m, nelem_, nrows_, nodes.data(), h_lids_.data(), offs.data());
+  subgrid_m_ = m;
+}
+
+// The fused element step of a subgrid layout (kernels/swhdg_subgrid_fused.hip): outputs per macro element.
+void AssemblyManager::swhdgCondensedSubgrid(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
+                                            const uint8_t *side_types, const double *farfield, SwhFusedOut o) {
+  requireReady(false);
+  shallowwaterHybridized *sw = dynamic_cast<shallowwaterHybridized *>(physics_.get());
+  MHA_REQUIRE(sw != nullptr, MHA_ERR_INVALID, "the block's physics module is not shallowwaterHybridized");
+  MHA_REQUIRE(subgrid_m_ > 0, MHA_ERR_STATE, "no subgrid layout: call mha_swhdg_set_subgrids first");
+  MHA_REQUIRE(lambda != nullptr, MHA_ERR_INVALID, "null trace values");
+  bindState(u, u_prev, u_stage);
+  prepareSideTables();
+  SwhElementDev a;
+  a.lambda = lambda;
+  a.side_types = side_types;
+  if (farfield) for (int i = 0; i < 3; ++i) a.farfield[i] = farfield[i];
+  a.g = sw->gravity;
+  a.roe = sw->roestab ? 1 : 0;
+  PhysParamsDev pp;
+  pp.physics = MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED;
+  const char *names[3] = {"source H", "source Hux", "source Huy"};
+  for (int k = 0; k < 3; ++k) pp.f[k] = functions_.evaluate(names[k]);
+  pp.p[0] = sw->gravity;
+  timedBegin();
+  launch_swhdg_subgrid_fused(subgrid_m_, blockDev(), sideTablesDev(), a, time_, pp, o, stream_);
+  timedEnd();
+}
+
+// The uncondensed blocks of a subgrid layout by the plain kernel (kernels/swhdg_subgrid_blocks.hip).
+void AssemblyManager::swhdgSubgridBlocks(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
+                                         const uint8_t *side_types, const double *farfield, double *res, double *blocks) {
+  requireReady(false);
+  shallowwaterHybridized *sw = dynamic_cast<shallowwaterHybridized *>(physics_.get());
+  MHA_REQUIRE(sw != nullptr, MHA_ERR_INVALID, "the block's physics module is not shallowwaterHybridized");
+  MHA_REQUIRE(subgrid_m_ > 0, MHA_ERR_STATE, "no subgrid layout: call mha_swhdg_set_subgrids first");
+  MHA_REQUIRE(lambda && (res || blocks), MHA_ERR_INVALID, "null trace values or outputs");
+  bindState(u, u_prev, u_stage);
+  prepareSideTables();
+  SwhElementDev a;
+  a.lambda = lambda;
+  a.side_types = side_types;
+  if (farfield) for (int i = 0; i < 3; ++i) a.farfield[i] = farfield[i];
+  a.g = sw->gravity;
+  a.roe = sw->roestab ? 1 : 0;
+  a.res = res;
+  a.blocks = blocks;
+  PhysParamsDev pp;
+  pp.physics = MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED;
+  const char *names[3] = {"source H", "source Hux", "source Huy"};
+  for (int k = 0; k < 3; ++k) pp.f[k] = functions_.evaluate(names[k]);
+  pp.p[0] = sw->gravity;
+  timedBegin();
+  launch_swhdg_subgrid_blocks(subgrid_m_, blockDev(), sideTablesDev(), a, time_, pp, stream_);
+  timedEnd();
+}
+
 // Workspace of subgridSolve (doubles unless noted): blocks [E][36][36], res [E][36], local_J [E][12][12], local_res
 // [E][12], du [E][12], rn0 [E], then int32 active [E].
 size_t AssemblyManager::subgridWorkspaceBytes() const {
+  if (subgrid_m_ > 0) {  // subgrid layout: the fused kernel keeps everything but the loop state on the chip: rn0, active per macro element
+    const size_t Em = static_cast<size_t>(nelem_) / (subgrid_m_ * subgrid_m_);
+    return (sizeof(double) + sizeof(int32_t)) * Em + 64;
+  }
   const size_t E = static_cast<size_t>(nelem_), ni = static_cast<size_t>(n_), n = ni + 24;
   return sizeof(double) * E * (n * n + n + ni * ni + ni + ni + 1) + sizeof(int32_t) * E + 64;
 }
@@ -1115,6 +1194,34 @@ void AssemblyManager::subgridSolve(double *u, const double *u_prev, const double
   MHA_REQUIRE(max_iter >= 1 && tol >= 0.0, MHA_ERR_INVALID, "bad iteration limits");
   MHA_REQUIRE(workspace_bytes >= subgridWorkspaceBytes(), MHA_ERR_INVALID,
               "workspace too small: " << workspace_bytes << " < " << subgridWorkspaceBytes());
+  if (subgrid_m_ > 0) {
+    // a subgrid layout is set: one workgroup per macro element and pass (kernels/swhdg_subgrid_fused.hip), the same protocol
+    // with norms and du over the n_int unknowns of a macro element; iters / resnorm / schur / gvec are per macro element
+    const size_t Em = static_cast<size_t>(nelem_) / (subgrid_m_ * subgrid_m_);
+    double *rn0 = static_cast<double *>(workspace);
+    MHA_HIP(hipMemsetAsync(num_singular, 0, sizeof(int32_t), stream_));
+    SwhFusedOut o;
+    o.singular = num_singular;
+    o.tol = tol;
+    o.rn0 = rn0;
+    o.scaled = resnorm_scaled;
+    o.iters = iters;
+    o.active = reinterpret_cast<int32_t *>(rn0 + Em);
+    for (int pass = 0; pass < max_iter; ++pass) {
+      o.pass = pass;
+      o.update_u = u;
+      swhdgCondensedSubgrid(u, u_prev, u_stage, lambda, side_types, farfield, o);
+    }
+    if (schur || gvec) {
+      o.pass = -1;
+      o.update_u = nullptr;
+      o.active = nullptr;
+      o.schur = schur;
+      o.gvec = gvec;
+      swhdgCondensedSubgrid(u, u_prev, u_stage, lambda, side_types, farfield, o);
+    }
+    return;
+  }
   if (!subgrid_checked_) {  // interior unknowns must be element-local (discontinuous): checked once per mesh
     std::vector<char> seen(nrows_, 0);
     for (size_t k = 0; k < h_lids_.size(); ++k) {

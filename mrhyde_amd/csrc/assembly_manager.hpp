@@ -63,6 +63,14 @@ class AssemblyManager {
   void subgridSolve(double *u, const double *u_prev, const double *u_stage, const double *lambda, const uint8_t *side_types,
                     const double *farfield, int max_iter, double tol, void *workspace, size_t workspace_bytes, double *schur,
                     double *gvec, int32_t *iters, double *resnorm_scaled, int32_t *num_singular);
+  // HDG subgrids of m x m sub-elements per macro element (kernels/swhdg_subgrid.hpp): the layout (validated on the host;
+  // m = 0 clears it), the fused element step, the uncondensed blocks of the plain kernel
+  void swhdgSetSubgrids(int m);
+  int swhdgSubgrids() const { return subgrid_m_; }
+  void swhdgCondensedSubgrid(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
+                             const uint8_t *side_types, const double *farfield, SwhFusedOut out);
+  void swhdgSubgridBlocks(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
+                          const uint8_t *side_types, const double *farfield, double *res, double *blocks);
   void scatterLocal(const double *local_J, const double *local_res, double *res, double *crs_vals);
   // boundary groups (reference: src/tools/boundaryGroup.hpp, assemblyManager.cpp:2518-2638)
   int addBoundaryGroup(const std::string &sidename, int bc_type, int num, const int32_t *elem_ids,
@@ -274,6 +282,7 @@ class AssemblyManager {
   DeviceBuffer<int32_t> d_db_index_, d_pos_var_;
   std::vector<int8_t> h_orient_;
   bool subgrid_checked_ = false;
+  int subgrid_m_ = 0;  // sub-elements per direction of an HDG subgrid layout, 0 = none (swhdgSetSubgrids)
   // per-variable views (multi-variable blocks): reference tables at the volume / side points, physical basis arrays
   struct VarTables { DeviceBuffer<double> val, grad, div; bool ready = false; };
   struct VarViews { DeviceBuffer<double> basis, grad, div; };

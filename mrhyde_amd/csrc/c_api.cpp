@@ -538,6 +538,50 @@ int mha_swhdg_condensed_element(mha_context *ctx, const double *u, const double 
   });
 }
 
+int mha_swhdg_set_subgrids(mha_context *ctx, int m) {
+  return guarded([&] { mgr(ctx).swhdgSetSubgrids(m); });
+}
+
+int mha_test_swhdg_check_subgrids(int m, int num_elems, int num_rows, const double *nodes, const int32_t *lids,
+                                  const int32_t *offsets) {
+  return guarded([&] { mha::check_swhdg_subgrids(m, num_elems, num_rows, nodes, lids, offsets); });
+}
+
+int mha_swhdg_condensed_subgrid(mha_context *ctx, const double *u, const double *u_prev, const double *u_stage,
+                                const double *lambda, const uint8_t *side_types, const double *farfield_host, double *schur,
+                                double *gvec, double *du, int32_t *num_singular) {
+  return guarded([&] {
+    MHA_REQUIRE(schur || gvec || du, MHA_ERR_INVALID, "no output requested");
+    mha::SwhFusedOut o;
+    o.schur = schur;
+    o.gvec = gvec;
+    o.du = du;
+    o.singular = num_singular;
+    mgr(ctx).swhdgCondensedSubgrid(u, u_prev, u_stage, lambda, side_types, farfield_host, o);
+  });
+}
+
+int mha_swhdg_subgrid_blocks(mha_context *ctx, const double *u, const double *u_prev, const double *u_stage,
+                             const double *lambda, const uint8_t *side_types, const double *farfield_host, double *res,
+                             double *blocks) {
+  return guarded([&] { mgr(ctx).swhdgSubgridBlocks(u, u_prev, u_stage, lambda, side_types, farfield_host, res, blocks); });
+}
+
+int mha_mesh_swhdg_subgrids_sizes(const int *ncell_macro, int m, int *nelem, int64_t *ndof, int64_t *ntrace) {
+  return guarded([&] {
+    MHA_REQUIRE(ncell_macro && nelem && ndof && ntrace, MHA_ERR_INVALID, "null argument");
+    mha::mesh_swhdg_subgrids_sizes(ncell_macro, m, nelem, ndof, ntrace);
+  });
+}
+
+int mha_mesh_swhdg_subgrids(const int *ncell_macro, int m, const double *lo, const double *hi, double *nodes, int32_t *lids,
+                            int32_t *offsets, int32_t *trace_lids) {
+  return guarded([&] {
+    MHA_REQUIRE(ncell_macro && lo && hi && nodes && lids && offsets && trace_lids, MHA_ERR_INVALID, "null argument");
+    mha::mesh_swhdg_subgrids(ncell_macro, m, lo, hi, nodes, lids, offsets, trace_lids);
+  });
+}
+
 int mha_swhdg_eigendecomp(double g, int64_t npts, const double *Shat, const double *normals, double *L, double *lam,
                           double *R, void *hip_stream) {
   return guarded([&] {

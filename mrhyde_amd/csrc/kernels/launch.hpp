@@ -156,6 +156,12 @@ void launch_dirichlet_lift(int64_t n, const uint8_t *fixed, const double *vals, 
 // swhdg_fused.hip: side + volume assembly + static condensation of the HDG element in one kernel
 void launch_swhdg_fused(const BlockDev &b, const SideTablesDev &st, const SwhElementDev &a, const TimeDev &tm,
                         const PhysParamsDev &pp, const SwhFusedOut &o, hipStream_t stream);
+// swhdg_subgrid_fused.hip: the same step for a subgrid of m x m sub-elements per macro element (one workgroup per macro
+// element, the assembled block in LDS); swhdg_subgrid_blocks.hip: its uncondensed block, plain and unfused (a.res, a.blocks)
+void launch_swhdg_subgrid_fused(int m, const BlockDev &b, const SideTablesDev &st, const SwhElementDev &a, const TimeDev &tm,
+                                const PhysParamsDev &pp, const SwhFusedOut &o, hipStream_t stream);
+void launch_swhdg_subgrid_blocks(int m, const BlockDev &b, const SideTablesDev &st, const SwhElementDev &a, const TimeDev &tm,
+                                 const PhysParamsDev &pp, hipStream_t stream);
 void launch_condense(int n_int, int n_trace, int64_t nelem, const double *blocks, const double *res, double *schur,
                      double *gvec, double *du, int *singular, hipStream_t stream);
 

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <thread>
 
 #include "common.hpp"
@@ -330,6 +331,107 @@ void mesh_structured_multi(int dim, const int *nc, const double *lo, const doubl
         }
       }
     }
+  }
+}
+
+void mesh_swhdg_subgrids_sizes(const int *nc, int m, int *nelem, int64_t *ndof, int64_t *ntrace) {
+  MHA_REQUIRE(nc[0] > 0 && nc[1] > 0 && m >= 1, MHA_ERR_INVALID, "subgrid mesh: ncell_macro and m must be positive");
+  const int64_t Em = static_cast<int64_t>(nc[0]) * nc[1];
+  MHA_REQUIRE(Em * m * m < (int64_t{1} << 31) / 12, MHA_ERR_INVALID, "subgrid mesh: too many elements for 32-bit LIDs");
+  *nelem = static_cast<int>(Em * m * m);
+  *ndof = Em * 3 * (m + 1) * (m + 1);
+  *ntrace = 6 * (static_cast<int64_t>(nc[0] + 1) * nc[1] + static_cast<int64_t>(nc[0]) * (nc[1] + 1));
+}
+
+void mesh_swhdg_subgrids(const int *nc, int m, const double *lo, const double *hi, double *nodes, int32_t *lids,
+                         int32_t *offsets, int32_t *trace_lids) {
+  int nelem;
+  int64_t ndof, ntrace;
+  mesh_swhdg_subgrids_sizes(nc, m, &nelem, &ndof, &ntrace);
+  const int nx = nc[0], ny = nc[1], np = (m + 1) * (m + 1);
+  static const int shv[4] = {0, 1, 3, 2};  // dof (x fastest) -> shards vertex
+  for (int v = 0; v < 3; ++v)
+    for (int dof = 0; dof < 4; ++dof) offsets[v * 4 + dof] = shv[dof] * 3 + v;
+  const double hx = (hi[0] - lo[0]) / nx, hy = (hi[1] - lo[1]) / ny;
+  const int nvert = (nx + 1) * ny;  // macro edges at x = const come first, then those at y = const
+  static const int vx[4] = {0, 1, 1, 0}, vy[4] = {0, 0, 1, 1};
+  for (int J = 0; J < ny; ++J)
+    for (int I = 0; I < nx; ++I) {
+      const int k = J * nx + I;
+      for (int ey = 0; ey < m; ++ey)
+        for (int ex = 0; ex < m; ++ex) {
+          const size_t e = static_cast<size_t>(k) * m * m + ey * m + ex;
+          for (int sv = 0; sv < 4; ++sv) {
+            const int ax = ex + vx[sv], ay = ey + vy[sv];
+            nodes[(e * 4 + sv) * 2] = lo[0] + hx * (I + static_cast<double>(ax) / m);
+            nodes[(e * 4 + sv) * 2 + 1] = lo[1] + hy * (J + static_cast<double>(ay) / m);
+            for (int v = 0; v < 3; ++v) lids[e * 12 + sv * 3 + v] = static_cast<int32_t>((static_cast<int64_t>(k) * np + ay * (m + 1) + ax) * 3 + v);
+          }
+        }
+      const int edges[4] = {J * (nx + 1) + I, nvert + J * nx + I, J * (nx + 1) + I + 1, nvert + (J + 1) * nx + I};
+      for (int v = 0; v < 3; ++v)
+        for (int ed = 0; ed < 4; ++ed)
+          for (int f = 0; f < 2; ++f) trace_lids[static_cast<size_t>(k) * 24 + (v * 4 + ed) * 2 + f] = (edges[ed] * 3 + v) * 2 + f;
+    }
+}
+
+void check_swhdg_subgrids(int m, int nelem, int nrows, const double *nodes, const int32_t *lids, const int32_t *offs) {
+  MHA_REQUIRE(m >= 1 && m <= 4, MHA_ERR_INVALID,
+              "HDG subgrids: m = " << m << " sub-elements per direction is outside 1..4 (the dense interior solve holds n_int = 3 (m+1)^2 <= 75 unknowns in LDS)");
+  MHA_REQUIRE(nelem > 0 && nrows > 0 && nodes && lids && offs, MHA_ERR_INVALID, "HDG subgrids: null or empty mesh");
+  const int m2 = m * m, np = (m + 1) * (m + 1);
+  MHA_REQUIRE(nelem % m2 == 0, MHA_ERR_INVALID, "HDG subgrids: " << nelem << " elements are not whole " << m << " x " << m << " sub-meshes");
+  const int Em = nelem / m2;
+  for (int i = 0; i < 12; ++i)
+    MHA_REQUIRE(offs[i] >= 0 && offs[i] < 12, MHA_ERR_INVALID, "HDG subgrids: offset " << offs[i] << " of (variable, dof) " << i << " is outside [0,12)");
+  for (size_t i = 0; i < static_cast<size_t>(nelem) * 12; ++i)
+    MHA_REQUIRE(lids[i] >= 0 && lids[i] < nrows, MHA_ERR_INVALID, "HDG subgrids: LID out of range: " << lids[i]);
+  std::vector<int32_t> owner(nrows, -1), rowof(3 * np);
+  for (int k = 0; k < Em; ++k) {
+    const int e0 = k * m2;
+    std::fill(rowof.begin(), rowof.end(), -1);
+    for (int ey = 0; ey < m; ++ey)
+      for (int ex = 0; ex < m; ++ex)
+        for (int v = 0; v < 3; ++v)
+          for (int aa = 0; aa < 4; ++aa) {
+            const int node = (ey + (aa >> 1)) * (m + 1) + ex + (aa & 1);
+            const int32_t row = lids[static_cast<size_t>(e0 + ey * m + ex) * 12 + offs[v * 4 + aa]];
+            int32_t &slot = rowof[v * np + node];
+            MHA_REQUIRE(slot < 0 || slot == row, MHA_ERR_INVALID,
+                        "HDG subgrids: macro element " << k << " is not a Q1 " << m << " x " << m << " sub-mesh: node " << node
+                                                       << " of variable " << v << " has rows " << slot << " and " << row);
+            slot = row;
+          }
+    for (int i = 0; i < 3 * np; ++i) {
+      const int32_t row = rowof[i];
+      MHA_REQUIRE(owner[row] != k, MHA_ERR_INVALID,
+                  "HDG subgrids: macro element " << k << " is not a Q1 " << m << " x " << m << " sub-mesh: row " << row
+                                                 << " belongs to two of its (variable, node) unknowns");
+      MHA_REQUIRE(owner[row] < 0, MHA_ERR_INVALID,
+                  "HDG subgrids: row " << row << " is shared by macro elements " << owner[row] << " and " << k
+                                       << ": interior unknowns belong to one macro element, once");
+      owner[row] = k;
+    }
+    // geometry: shards vertices 0..3 of sub-element (ex, ey) against the bilinear image of the uniform subdivision
+    auto vert = [&](int ex, int ey, int sv) { return &nodes[(static_cast<size_t>(e0 + ey * m + ex) * 4 + sv) * 2]; };
+    const double *c00 = vert(0, 0, 0), *c10 = vert(m - 1, 0, 1), *c11 = vert(m - 1, m - 1, 2), *c01 = vert(0, m - 1, 3);
+    double size = 0.0;
+    for (const double *pq : {c10, c11, c01}) size = std::max(size, std::hypot(pq[0] - c00[0], pq[1] - c00[1]));
+    size = std::max(size, std::hypot(c11[0] - c10[0], c11[1] - c10[1]));
+    static const int sx[4] = {0, 1, 1, 0}, sy[4] = {0, 0, 1, 1};
+    for (int ey = 0; ey < m; ++ey)
+      for (int ex = 0; ex < m; ++ex)
+        for (int sv = 0; sv < 4; ++sv) {
+          const double s = static_cast<double>(ex + sx[sv]) / m, t = static_cast<double>(ey + sy[sv]) / m;
+          const double *p = vert(ex, ey, sv);
+          for (int d = 0; d < 2; ++d) {
+            const double want = (1 - s) * (1 - t) * c00[d] + s * (1 - t) * c10[d] + s * t * c11[d] + (1 - s) * t * c01[d];
+            MHA_REQUIRE(std::fabs(p[d] - want) <= 1e-12 * size, MHA_ERR_INVALID,
+                        "HDG subgrids: macro element " << k << ": the sub-mesh is not the bilinear image of the uniform " << m << " x " << m
+                                                       << " subdivision (sub-element " << ey * m + ex << ", vertex " << sv << " is off by "
+                                                       << std::fabs(p[d] - want) << ")");
+          }
+        }
   }
 }
 

@@ -22,6 +22,21 @@ void mesh_structured_multi(int dim, const int *ncell, const double *lo, const do
                            const int *orders, double *verts, int32_t *cell2vert, int32_t *lids, int32_t *offsets,
                            int8_t *orient, uint8_t *side_mask, int32_t *dof_var);
 
+// HDG subgrid mesh of shallowwaterHybridized: ncell_macro[2] macro quads on [lo, hi], each an m x m sub-mesh of three order-1
+// HGRAD variables that are continuous inside a macro element and discontinuous across macro elements.  Elements
+// [k m^2, (k+1) m^2) are macro element k's sub-elements, row-major with x fastest; nodes[E][4][2] in shards vertex order;
+// lids[E][12] / offsets[12] in the subcell-major convention of mesh_structured_multi (vertex-major, variables interleaved);
+// trace_lids[Em][24] = (variable, HFACE edge left/bottom/right/top, function) -> row of the macro trace system, an edge's
+// two functions numbered along +x / +y for both of its macro elements.  ndof = Em 3 (m+1)^2, ntrace = 6 x macro edges.
+void mesh_swhdg_subgrids_sizes(const int *ncell_macro, int m, int *nelem, int64_t *ndof, int64_t *ntrace);
+void mesh_swhdg_subgrids(const int *ncell_macro, int m, const double *lo, const double *hi, double *nodes, int32_t *lids,
+                         int32_t *offsets, int32_t *trace_lids);
+
+// The layout check of mha_swhdg_set_subgrids (throws MHA_ERR_INVALID): elements [k m^2, (k+1) m^2) are macro element k's
+// m x m sub-mesh, row-major with x fastest; its rows are shared only inside k with the Q1 connectivity of an m x m grid;
+// its vertices are the bilinear image of the uniform subdivision of the macro quad to 1e-12 x its size.  m in 1..4.
+void check_swhdg_subgrids(int m, int nelem, int nrows, const double *nodes, const int32_t *lids, const int32_t *offsets);
+
 // Overlapped CRS graph: every dof of an element couples to every dof of that element;
 // columns ascending (reference: src/interfaces/linearAlgebraInterface.cpp:218-229).
 void build_crs_graph(int nrows, int nelem, int n, const int32_t *lids, std::vector<int32_t> &rowptr,

@@ -69,6 +69,11 @@ int mha_test_block_pattern_step_plan(int dim, int num_rows, int num_elems, int n
                                      int64_t stores_len, int32_t *rep_stores, int64_t rep_stores_len, int32_t *segs,
                                      int64_t segs_len, int32_t *items, int64_t items_len, int *counts);
 
+/* The layout check of mha_swhdg_set_subgrids alone (mesh.hpp, check_swhdg_subgrids), on host arrays in mha_set_mesh
+ * form: nodes [num_elems][4][2], lids [num_elems][12], offsets [12].  Stateless. */
+int mha_test_swhdg_check_subgrids(int m, int num_elems, int num_rows, const double *nodes, const int32_t *lids,
+                                  const int32_t *offsets);
+
 #ifdef __cplusplus
 }
 #endif
