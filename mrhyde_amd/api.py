@@ -600,6 +600,92 @@ def block_pattern_step_plan(dim, nodes, lids, nrows, rowptr, colind, khat, facto
     return (full, db, stores, rep_stores[:info["rep_entries"]], segs[:info["segments"]], items[:info["items"]], info)
 
 
+def k1_plan(dim, lids, offsets, geo, order="auto", row_budget=0):
+    """Host-only test hook: the plan of the workgroup-merged residual kernel (csrc/row_owner_plan.hpp) for the geometry
+    records geo [E][20].  order: "auto", "natural" or "morton"; row_budget 0: the kernel's.  -> dict(wg_elems [G*256],
+    row_ptr [G+1], rows, loc [G][n][256], max_rows, axis_aligned, morton)."""
+    lids, offsets, geo = _np(lids, np.int32), _np(offsets, np.int32), _np(geo, np.float64)
+    ne, n = lids.shape
+    assert geo.shape == (ne, 20)
+    G = (ne + 255) // 256
+    out = dict(wg_elems=np.zeros(G * 256, np.int32), row_ptr=np.zeros(G + 1, np.int32), rows=np.zeros(ne * n, np.int32),
+               loc=np.zeros((G, n, 256), np.uint16))
+    counts = (C.c_int * 4)()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    f = load_library().mha_test_k1_plan
+    f.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_int] * 2 + [C.c_void_p] * 5
+    _check(f(ne, n, int(dim), vp(lids), vp(offsets), vp(geo), ("auto", "natural", "morton").index(order), int(row_budget),
+             vp(out["wg_elems"]), vp(out["row_ptr"]), vp(out["rows"]), vp(out["loc"]), counts))
+    out["rows"] = out["rows"][:counts[0]]
+    out.update(max_rows=counts[1], axis_aligned=bool(counts[2]), morton=bool(counts[3]))
+    return out
+
+
+def distinct_shapes(dim, geo):
+    """Host-only test hook: the bit-exact geometry-shape database of geo [E][20].  -> (shapes [count][16], index [E])."""
+    geo = _np(geo, np.float64)
+    shapes, index, count = np.zeros((geo.shape[0], 16)), np.zeros(geo.shape[0], np.int32), C.c_int()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    f = load_library().mha_test_distinct_shapes
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3
+    _check(f(vp(geo), geo.shape[0], int(dim), vp(shapes), vp(index), C.byref(count)))
+    return shapes[:count.value], index
+
+
+def pair_lid_slots(emask, n):
+    """Host-only test hook: LID slots paired by co-ownership from the ownership masks.  -> int32 [2*ceil(n/2)]."""
+    emask = _np(emask, np.int32)
+    pairs = np.zeros(2 * ((n + 1) // 2), np.int32)
+    f = load_library().mha_test_pair_lid_slots
+    f.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    _check(f(emask.ctypes.data_as(C.c_void_p), len(emask), int(n), pairs.ctypes.data_as(C.c_void_p)))
+    return pairs
+
+
+def collocation_derivative(order):
+    """Host-only test hook: the 1-D collocation derivative of the residual kernel and the 1-D tables it was made from.
+    -> (dcol [q][q'], phi [i][q], dphi [i][q]), each [order+1][order+1]."""
+    m = order + 1
+    dcol, phi, dphi = np.zeros((m, m)), np.zeros((m, m)), np.zeros((m, m))
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    f = load_library().mha_test_collocation_derivative
+    f.argtypes = [C.c_int] + [C.c_void_p] * 3
+    _check(f(int(order), vp(dcol), vp(phi), vp(dphi)))
+    return dcol, phi, dphi
+
+
+def porous_direct_plan(lids, offsets, nrows, rowptr, colind):
+    """Host-only test hook: the plan of the porousMixed direct form (csrc/porous_plan.hpp); raises MhaError with the reason
+    when the mesh does not allow it.  -> (side [E][n], diag [nrows])."""
+    lids, offsets, rowptr, colind = _np(lids, np.int32), _np(offsets, np.int32), _np(rowptr, np.int32), _np(colind, np.int32)
+    side, diag = np.zeros(lids.shape, np.uint8), np.zeros(nrows, np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    f = load_library().mha_test_porous_direct_plan
+    f.argtypes = [C.c_int] * 3 + [C.c_void_p] * 6
+    _check(f(int(nrows), lids.shape[0], lids.shape[1], vp(lids), vp(offsets), vp(rowptr), vp(colind), vp(side), vp(diag)))
+    return side, diag
+
+
+def porous_database_plan(nodes, lids, offsets, nrows, rowptr, colind, slot, orient=None, fixed=None):
+    """Host-only test hook: the plan of the porousMixed database mode; raises MhaError with the reason when the block does
+    not allow it.  slot [E][n][n]: position of column lids[e][j] in row lids[e][i].  -> dict(axis_aligned, jacflag [E],
+    elist, diag [nrows], runs [k][3] = (source, destination, length), num_classes, computed_rows)."""
+    nodes, lids, offsets = _np(nodes, np.float64), _np(lids, np.int32), _np(offsets, np.int32)
+    rowptr, colind, slot = _np(rowptr, np.int32), _np(colind, np.int32), _np(slot, np.uint8)
+    ori = None if orient is None else _np(orient, np.int8)
+    fx = None if fixed is None else _np(fixed, np.uint8)
+    ne, n = lids.shape
+    jacflag, elist, diag = np.zeros(ne, np.uint8), np.zeros(ne, np.int32), np.zeros(nrows, np.int32)
+    runs, counts = np.zeros((len(colind) + 1, 3), np.int64), np.zeros(5, np.int64)
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    f = load_library().mha_test_porous_database_plan
+    f.argtypes = [C.c_int] * 5 + [C.c_void_p] * 12 + [C.c_int64, C.c_void_p]
+    _check(f(int(nrows), ne, n, nodes.shape[1], nodes.shape[2], vp(lids), vp(offsets), vp(rowptr), vp(colind), vp(nodes),
+             vp(ori), vp(fx), vp(slot), vp(jacflag), vp(elist), vp(diag), vp(runs), runs.size, vp(counts)))
+    return dict(axis_aligned=bool(counts[0]), jacflag=jacflag, elist=elist[:counts[1]], diag=diag, runs=runs[:counts[2]],
+                num_classes=int(counts[3]), computed_rows=int(counts[4]))
+
+
 def row_partition(dim, nodes, lids, nrows, rowptr, caps=None):
     """Host-only: the row-owner partition (mha_row_partition_*).  -> dict(row_ptr, rows, elem_ptr, elems, max_*)."""
     lib = load_library()

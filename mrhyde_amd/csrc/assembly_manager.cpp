@@ -1,6 +1,5 @@
 #include "assembly_manager.hpp"
 
-#include <cstring>
 #include <unordered_map>
 
 #include <algorithm>
@@ -9,8 +8,9 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "mesh.hpp"
 #include "porous_data.hpp"
+#include "porous_plan.hpp"
+#include "row_owner_plan.hpp"
 
 namespace mha {
 
@@ -120,6 +120,9 @@ void AssemblyManager::setMesh(int nelem, const double *nodes, const int32_t *lid
   d_nodes_.upload(nodes, static_cast<size_t>(nelem) * nnodes_ * dim_);
   d_lids_.upload(lids, nl);
   d_offsets_.upload(offsets, n_);
+  h_offsets_.assign(offsets, offsets + n_);
+  h_p2d_.assign(n_, 0);
+  for (int f = 0; f < n_; ++f) h_p2d_[offsets[f]] = f;
   has_fixed_ = fixed != nullptr;
   if (fixed) h_fixed_.assign(fixed, fixed + nrows);
   if (fixed) d_fixed_.upload(fixed, nrows);
@@ -204,37 +207,36 @@ void AssemblyManager::setOrientation(const int8_t *signs) {
   db_index_.clear();
 }
 
-void AssemblyManager::prepareRowGather(bool need_jacobian, bool dense) {
+std::vector<double> AssemblyManager::hostNodes() const {
+  std::vector<double> nodes(static_cast<size_t>(nelem_) * nnodes_ * dim_);
+  d_nodes_.download(nodes.data());
+  return nodes;
+}
+
+// row -> (element, position) incidences, built once per mesh / graph: the host copy and the row gather's device copies
+const RowIncidence &AssemblyManager::rowIncidence() {
   if (!has_incidence_) {
-    std::vector<int32_t> ptr, elem, lpos;
-    build_row_incidence(nrows_, nelem_, n_, h_lids_.data(), ptr, elem, lpos);
-    d_inc_ptr_.upload(ptr);
-    d_inc_elem_.upload(elem);
-    d_inc_pos_.upload(lpos);
-    std::vector<int32_t> offs(n_), p2d(n_, 0);
-    d_offsets_.download(offs.data());
-    for (int f = 0; f < n_; ++f) p2d[offs[f]] = f;
-    std::vector<int32_t> ldof(lpos.size());
-    for (size_t k = 0; k < lpos.size(); ++k) ldof[k] = p2d[lpos[k]];
+    build_row_incidence(nrows_, nelem_, n_, h_lids_.data(), inc_.ptr, inc_.elem, inc_.lpos);
+    d_inc_ptr_.upload(inc_.ptr);
+    d_inc_elem_.upload(inc_.elem);
+    d_inc_pos_.upload(inc_.lpos);
+    std::vector<int32_t> ldof(inc_.lpos.size());
+    for (size_t k = 0; k < ldof.size(); ++k) ldof[k] = h_p2d_[inc_.lpos[k]];
     d_inc_dof_.upload(ldof);
-    max_row_ = 0;
-    for (int r = 0; r < nrows_; ++r) max_row_ = std::max(max_row_, h_rowptr_[r + 1] - h_rowptr_[r]);
     has_incidence_ = true;
   }
+  return inc_;
+}
+
+void AssemblyManager::prepareRowGather(bool need_jacobian, bool dense) {
+  rowIncidence();
   prepareElemSlots();
   if (!dense) return;  // (the direct form of porousMixed needs the incidences and the slot map only)
   if (need_jacobian) d_gather_J_.resize(static_cast<size_t>(nelem_) * n_ * n_);
   d_gather_res_.resize(static_cast<size_t>(nelem_) * n_);
 }
 
-// Database mode of the direct form.  Preconditions, checked once per mesh / graph (the coefficient kinds per assembly):
-// every element has the same vertex offsets from its first vertex and the same orientation signs, bit for bit (then the
-// direct kernel, which works on relative coordinates, produces the same matrix for every element).  Rows are classified
-// by what determines their values: fixed flag, and per incident element its local dof and the slots of the element's
-// columns in the row.  Per class the first run of >= 2 K consecutive rows gives K = ceil(128 / len) + 2 representative
-// rows (enough for any 1 KB chunk to be sourced contiguously from their periodic image); every other row of a class that
-// has representatives is REPLICATED; the rest (fixed rows, short or rare classes, the representatives) are COMPUTED as
-// before, by the elements incident to them.
+// Database mode of the direct form (porous_plan.hpp), decided once per mesh / graph (the coefficient kinds per assembly).
 bool AssemblyManager::porousDatabaseUsable() {
   PorousDatabase &db = porous_db_;
   if (db.state >= 0) return db.state == 1;
@@ -242,125 +244,31 @@ bool AssemblyManager::porousDatabaseUsable() {
   const char *m = std::getenv("MHA_POROUS_DATABASE");
   if (m && m[0] == '0') { db.why = "MHA_POROUS_DATABASE=0"; return false; }
   if (!porousDirectUsable() || elem_slot_bytes_ != 1) { db.why = "direct form not usable"; return false; }
-  const int nn = nnodes_, d = dim_;
-  std::vector<double> nodes(static_cast<size_t>(nelem_) * nn * d);
-  d_nodes_.download(nodes.data());
-  for (int e = 1; e < nelem_; ++e)
-    for (int k = 1; k < nn; ++k)
-      for (int c = 0; c < d; ++c) {
-        const double a = nodes[(static_cast<size_t>(e) * nn + k) * d + c] - nodes[static_cast<size_t>(e) * nn * d + c];
-        const double b0 = nodes[static_cast<size_t>(k) * d + c] - nodes[c];
-        if (std::memcmp(&a, &b0, sizeof(double)) != 0) { db.why = "elements of different shapes"; return false; }
-      }
-  if (has_orient_)
-    for (int e = 1; e < nelem_; ++e)
-      if (std::memcmp(&h_orient_[static_cast<size_t>(e) * n_], &h_orient_[0], n_) != 0) { db.why = "orientation signs differ between elements"; return false; }
-  {  // is the common shape an axis-aligned box?  (shards vertex order: bit pattern of vertex k = (k in {1,2,5,6}, k in {2,3,6,7}, k >= 4))
-    db.axis_aligned = true;
-    for (int k = 0; k < nn; ++k) {
-      const bool bit[3] = {k == 1 || k == 2 || k == 5 || k == 6, k == 2 || k == 3 || k == 6 || k == 7, k >= 4};
-      const int ref[3] = {1, 3, 4};  // the vertices one step from vertex 0 in x, y, z
-      for (int c = 0; c < d; ++c) {
-        const double rel = nodes[static_cast<size_t>(k) * d + c] - nodes[c];
-        const double want = bit[c] ? nodes[static_cast<size_t>(ref[c]) * d + c] - nodes[c] : 0.0;
-        if (rel != want) db.axis_aligned = false;
-      }
-    }
-  }
-  // ---- row classes ----
   prepareElemSlots();
   std::vector<uint8_t> slot(static_cast<size_t>(nelem_) * n_ * n_);
   MHA_HIP(hipStreamSynchronize(stream_));
   d_elem_slot_.download(slot.data());
-  std::vector<int32_t> ptr, elem, lpos, offs(n_), p2d(n_, 0);
-  build_row_incidence(nrows_, nelem_, n_, h_lids_.data(), ptr, elem, lpos);
-  d_offsets_.download(offs.data());
-  for (int f = 0; f < n_; ++f) p2d[offs[f]] = f;
-  std::unordered_map<std::string, int32_t> classes;
-  std::vector<int32_t> cls(nrows_, -1);
-  std::string key;
-  for (int r = 0; r < nrows_; ++r) {
-    if (has_fixed_ && h_fixed_[r]) continue;  // fixed rows: computed (zeroed) by the finishing pass
-    key.clear();
-    key.push_back(static_cast<char>(h_rowptr_[r + 1] - h_rowptr_[r]));
-    for (int k = ptr[r]; k < ptr[r + 1]; ++k) {
-      key.push_back(static_cast<char>(p2d[lpos[k]]));
-      const uint8_t *srow = &slot[(static_cast<size_t>(elem[k]) * n_ + lpos[k]) * n_];
-      for (int f = 0; f < n_; ++f) key.push_back(static_cast<char>(srow[offs[f]]));
-    }
-    cls[r] = classes.emplace(key, static_cast<int32_t>(classes.size())).first->second;
-  }
-  const int nc = static_cast<int>(classes.size());
-  std::vector<int32_t> rep_entry(nc, -1), len_of(nc, 0), K_of(nc, 0);
-  std::vector<uint8_t> replicated(nrows_, 0);
-  // pass 1: representatives = the first K rows of the first long run of a class
-  for (int r = 0; r < nrows_;) {
-    int r1 = r + 1;
-    while (r1 < nrows_ && cls[r1] == cls[r]) ++r1;
-    const int c = cls[r];
-    if (c >= 0 && rep_entry[c] < 0) {
-      const int len = h_rowptr_[r + 1] - h_rowptr_[r];
-      const int K = len > 0 ? (128 + len - 1) / len + 2 : 0;
-      if (len > 0 && r1 - r >= 2 * K) { rep_entry[c] = h_rowptr_[r]; len_of[c] = len; K_of[c] = K; for (int q = r + K; q < r1; ++q) replicated[q] = 1; }
-    }
-    r = r1;
-  }
-  // pass 2: every other row of a class that has representatives
-  for (int r = 0; r < nrows_; ++r) {
-    const int c = cls[r];
-    if (c < 0 || rep_entry[c] < 0 || replicated[r]) continue;
-    const bool is_rep = h_rowptr_[r] >= rep_entry[c] && h_rowptr_[r] < rep_entry[c] + K_of[c] * len_of[c];
-    if (!is_rep) replicated[r] = 1;
-  }
-  // copy runs of the replicated ranges (maximal runs of replicated rows of one class): the class's K representative
-  // rows repeat with period len, so every K * len entries of a range read the representatives from their first entry
-  std::vector<CopyRun> runs;
-  int64_t computed = 0;
-  for (int r = 0; r < nrows_;) {
-    if (!replicated[r]) { ++computed; ++r; continue; }
-    int r1 = r + 1;
-    while (r1 < nrows_ && replicated[r1] && cls[r1] == cls[r]) ++r1;
-    const int c = cls[r];
-    const int64_t dbeg = h_rowptr_[r], dend = h_rowptr_[r1], period = static_cast<int64_t>(K_of[c]) * len_of[c];
-    for (int64_t d0 = dbeg; d0 < dend; d0 += period) runs.push_back({rep_entry[c], d0, std::min(period, dend - d0)});
-    r = r1;
-  }
-  if (runs.empty()) { db.why = "no class has a run long enough to replicate"; return false; }
-  // elements incident to computed rows store their entries; diagonal positions of the computed face rows only
-  std::vector<uint8_t> jacflag(nelem_, 0);
-  std::vector<int32_t> diag(nrows_, -1);
-  for (int r = 0; r < nrows_; ++r) {
-    if (replicated[r]) continue;
-    bool face = false;
-    for (int k = ptr[r]; k < ptr[r + 1]; ++k) { jacflag[elem[k]] = 1; face = face || p2d[lpos[k]] > 0; }
-    if (face)
-      for (int k = h_rowptr_[r]; k < h_rowptr_[r + 1]; ++k)
-        if (h_colind_[k] == r) diag[r] = k;
-  }
-  db.jacflag.upload(jacflag);
-  {
-    std::vector<int32_t> elist;
-    for (int e = 0; e < nelem_; ++e)
-      if (jacflag[e]) elist.push_back(e);
-    db.num_listed = static_cast<int>(elist.size());
-    if (elist.empty()) elist.push_back(0);
-    db.elist.upload(elist);
-  }
-  db.diag.upload(diag);
-  const CopyPlan cp = build_copy_plan(std::move(runs), h_rowptr_[nrows_]);
+  PorousDatabasePlan p = porous_database_plan(nrows_, nelem_, n_, nnodes_, dim_, h_offsets_.data(), h_rowptr_.data(),
+                                              h_colind_.data(), hostNodes().data(), has_orient_ ? h_orient_.data() : nullptr,
+                                              has_fixed_ ? h_fixed_.data() : nullptr, slot.data(), rowIncidence());
+  if (!p.usable) { db.why = p.why; return false; }
+  db.axis_aligned = p.axis_aligned;
+  db.jacflag.upload(p.jacflag);
+  db.num_listed = static_cast<int>(p.elist.size());
+  if (p.elist.empty()) p.elist.push_back(0);
+  db.elist.upload(p.elist);
+  db.diag.upload(p.diag);
+  const CopyPlan cp = build_copy_plan(std::move(p.runs), h_rowptr_[nrows_]);
   db.copy_items.upload(cp.item);
   db.copy_segs.upload(cp.seg);
   db.num_items = cp.num_items();
   db.num_segs = cp.num_segs();
-  db.num_classes = nc;
-  db.computed_rows = computed;
+  db.num_classes = p.num_classes;
+  db.computed_rows = p.computed_rows;
   db.state = 1;
-  if (std::getenv("MHA_VERBOSE")) {
-    int64_t flagged = 0;
-    for (uint8_t f : jacflag) flagged += f;
-    fprintf(stderr, "[mrhyde_amd] porousMixed database mode: %d row classes, %lld of %d rows computed, %lld of %d elements store entries, %d copy spans, %d segments\n",
-            nc, (long long)computed, nrows_, (long long)flagged, nelem_, db.num_items, db.num_segs);
-  }
+  if (std::getenv("MHA_VERBOSE"))
+    fprintf(stderr, "[mrhyde_amd] porousMixed database mode: %d row classes, %lld of %d rows computed, %d of %d elements store entries, %d copy spans, %d segments\n",
+            db.num_classes, (long long)db.computed_rows, nrows_, db.num_listed, nelem_, db.num_items, db.num_segs);
   return true;
 }
 
@@ -369,9 +277,8 @@ void AssemblyManager::launchDatabaseCopy(double *crs_vals) {
                    h_rowptr_[nrows_], crs_vals, crs_vals, stream_);
 }
 
-// The direct form of the porousMixed assembly (kernels/porous_element.hip) rests on one property of the mesh: any two
-// elements share at most ONE dof (a face), so that a matrix entry (i, j), i != j, has one contributing element and a
-// row at most two.  Checked here on the LID lists, once per mesh / graph; anything else keeps the row gather.
+// The direct form of the porousMixed assembly (kernels/porous_element.hip), wherever the mesh allows it
+// (porous_plan.hpp); decided once per mesh / graph; anything else keeps the row gather.
 bool AssemblyManager::porousDirectUsable() {
   if (porous_direct_ >= 0) return porous_direct_ == 1;
   porous_direct_ = 0;
@@ -379,42 +286,11 @@ bool AssemblyManager::porousDirectUsable() {
   if (m && m[0] == '0') { porous_direct_why_ = "MHA_POROUS_DIRECT=0"; return false; }
   if (k && k[0] == 'e') { porous_direct_why_ = "point engine forced"; return false; }
   if (!physics_ || physics_->label != "porousMixed" || n_ != 1 + 2 * dim_) { porous_direct_why_ = "not the lowest-order mixed element"; return false; }
-  std::vector<int32_t> ptr, elem, lpos;
-  build_row_incidence(nrows_, nelem_, n_, h_lids_.data(), ptr, elem, lpos);
-  for (int r = 0; r < nrows_; ++r) {
-    const int ni = ptr[r + 1] - ptr[r];
-    if (ni > 2) { porous_direct_why_ = "a row with more than two incident elements"; return false; }
-    if (ni == 2) {
-      const int32_t *a = &h_lids_[static_cast<size_t>(elem[ptr[r]]) * n_], *b = &h_lids_[static_cast<size_t>(elem[ptr[r] + 1]) * n_];
-      int shared = 0;
-      for (int i = 0; i < n_; ++i)
-        for (int j = 0; j < n_; ++j) shared += a[i] == b[j];
-      if (shared != 1) { porous_direct_why_ = "two elements share more than one dof"; return false; }
-    }
-  }
-  for (int e = 0; e < nelem_; ++e)  // (an element listing a dof twice would add twice into one entry)
-    for (int i = 0; i < n_; ++i)
-      for (int j = i + 1; j < n_; ++j)
-        if (h_lids_[static_cast<size_t>(e) * n_ + i] == h_lids_[static_cast<size_t>(e) * n_ + j]) { porous_direct_why_ = "repeated dof in an element"; return false; }
-  // which incidence of its row an element is (dof order), and where the diagonal of a face row sits in the CRS
-  std::vector<int32_t> offs(n_), p2d(n_, 0);
-  d_offsets_.download(offs.data());
-  for (int f = 0; f < n_; ++f) p2d[offs[f]] = f;
-  std::vector<uint8_t> side(static_cast<size_t>(nelem_) * n_, 0);
-  std::vector<int32_t> diag(nrows_, -1);
-  for (int r = 0; r < nrows_; ++r) {
-    bool face = false;
-    for (int k = ptr[r]; k < ptr[r + 1]; ++k) {
-      const int d = p2d[lpos[k]];
-      side[static_cast<size_t>(elem[k]) * n_ + d] = static_cast<uint8_t>(k - ptr[r]);
-      face = face || d > 0;
-    }
-    if (face)
-      for (int k = h_rowptr_[r]; k < h_rowptr_[r + 1]; ++k)
-        if (h_colind_[k] == r) diag[r] = k;
-  }
-  d_direct_side_.upload(side);
-  d_direct_diag_.upload(diag);
+  PorousDirectPlan p = porous_direct_plan(nrows_, nelem_, n_, h_lids_.data(), h_offsets_.data(), h_rowptr_.data(),
+                                          h_colind_.data(), rowIncidence());
+  if (!p.usable) { porous_direct_why_ = p.why; return false; }
+  d_direct_side_.upload(p.side);
+  d_direct_diag_.upload(p.diag);
   porous_direct_ = 1;
   return true;
 }
@@ -454,6 +330,8 @@ void AssemblyManager::setGraph(const int32_t *rowptr, const int32_t *colind) {
   d_rowptr_.upload(h_rowptr_);
   d_colind_.upload(h_colind_);
   has_graph_ = true;
+  max_row_ = 0;
+  for (int r = 0; r < nrows_; ++r) max_row_ = std::max(max_row_, h_rowptr_[r + 1] - h_rowptr_[r]);
   ro_ = RowOwnerData();
   bpat_ = BlockPatternData();
   gro_ = GeneralRowOwnerData();
@@ -606,10 +484,8 @@ void AssemblyManager::bindState(const double *u, const double *u_prev, const dou
 // column search of sumIntoValues (assemblyManager.cpp:4138) in the general-element kernel
 void AssemblyManager::prepareElemSlots() {
   if (has_elem_slot_) return;
-  int max_row = 0;
-  for (int r = 0; r < nrows_; ++r) max_row = std::max(max_row, h_rowptr_[r + 1] - h_rowptr_[r]);
-  MHA_REQUIRE(max_row <= 65536, MHA_ERR_INVALID, "CRS rows longer than 65536 entries are not supported");
-  elem_slot_bytes_ = max_row <= 256 ? 1 : 2;
+  MHA_REQUIRE(max_row_ <= 65536, MHA_ERR_INVALID, "CRS rows longer than 65536 entries are not supported");
+  elem_slot_bytes_ = max_row_ <= 256 ? 1 : 2;
   d_elem_slot_.resize(static_cast<size_t>(nelem_) * n_ * n_ * elem_slot_bytes_);
   launch_build_elem_slot_map(blockDev(), d_elem_slot_.data(), elem_slot_bytes_, stream_);
   has_elem_slot_ = true;
@@ -935,8 +811,7 @@ void AssemblyManager::computeLocalJacRes(int compute_jacobian, const double *u, 
 // from the element's first vertex (bit patterns) + the orientation signs; representatives in order of first appearance
 int AssemblyManager::databaseBuild() {
   MHA_REQUIRE(has_mesh_, MHA_ERR_STATE, "no mesh: call mha_set_mesh first");
-  std::vector<double> nodes(static_cast<size_t>(nelem_) * nnodes_ * dim_);
-  d_nodes_.download(nodes.data());
+  const std::vector<double> nodes = hostNodes();
   const size_t kd = static_cast<size_t>(nnodes_ - 1) * dim_, ko = has_orient_ ? static_cast<size_t>(n_) : 0;
   const size_t kb = kd * sizeof(double) + ko;
   std::unordered_map<std::string, int32_t> seen;
@@ -993,10 +868,9 @@ void AssemblyManager::applyMassMatrixFree(int mode, const double *masswts, const
   if (mode == MHA_MASS_DATABASE_SPARSE) {
     MHA_REQUIRE(values && columns && nnz_row, MHA_ERR_INVALID, "sparse mass format needs a Sparse3DView");
     if (d_pos_var_.size() != static_cast<size_t>(n_)) {  // variable of every LID position (Sparse3DView::setLocalColumns)
-      std::vector<int32_t> offs(n_), pv(n_, 0);
-      d_offsets_.download(offs.data());
+      std::vector<int32_t> pv(n_, 0);
       for (int v = 0; v < layout_.nvars; ++v)
-        for (int j = layout_.varptr[v]; j < layout_.varptr[v + 1]; ++j) pv[offs[j]] = v;
+        for (int j = layout_.varptr[v]; j < layout_.varptr[v + 1]; ++j) pv[h_offsets_[j]] = v;
       d_pos_var_.upload(pv);
     }
   } else {
@@ -1102,11 +976,7 @@ void AssemblyManager::swhdgSetSubgrids(int m) {
               "HDG subgrids are built for 2-D shallowwaterHybridized blocks of three order-1 variables");
   MHA_REQUIRE(m >= 1 && m <= 4, MHA_ERR_INVALID,
               "HDG subgrids: m = " << m << " sub-elements per direction is outside 1..4 (the dense interior solve holds n_int = 3 (m+1)^2 <= 75 unknowns in LDS)");
-  std::vector<int32_t> offs(n_);
-  d_offsets_.download(offs.data());
-  std::vector<double> nodes(static_cast<size_t>(nelem_) * 8);
-  d_nodes_.download(nodes.data());
-  check_swhdg_subgrids(m, nelem_, nrows_, nodes.data(), h_lids_.data(), offs.data());
+  check_swhdg_subgrids(m, nelem_, nrows_, hostNodes().data(), h_lids_.data(), h_offsets_.data());
   subgrid_m_ = m;
 }
 
@@ -1911,8 +1781,8 @@ void AssemblyManager::importMeshData(int64_t npts, const double *points, int nco
   MHA_REQUIRE(has_mesh_, MHA_ERR_STATE, "mesh data before mha_set_mesh");
   MHA_REQUIRE(ncols >= 1, MHA_ERR_INVALID, "mesh data: ncols must be at least 1");
   MHA_REQUIRE(npts >= 1 && points && values, MHA_ERR_INVALID, "mesh data: no data points");
-  std::vector<double> nodes(static_cast<size_t>(nelem_) * nnodes_ * dim_), centres(static_cast<size_t>(nelem_) * dim_);
-  d_nodes_.download(nodes.data());
+  const std::vector<double> nodes = hostNodes();
+  std::vector<double> centres(static_cast<size_t>(nelem_) * dim_);
   const double wv = 1.0 / nnodes_;
   for (int e = 0; e < nelem_; ++e)
     for (int d = 0; d < dim_; ++d) {
@@ -1948,17 +1818,12 @@ void AssemblyManager::prepareRowOwner() {
   ro.num_affine_elems = 0;
   for (int e = 0; e < nelem_; ++e) ro.num_affine_elems += flags[e];
   // 2. row blocks
-  std::vector<double> nodes(static_cast<size_t>(nelem_) * nnodes_ * dim_);
-  d_nodes_.download(nodes.data());
+  const std::vector<double> nodes = hostNodes();
   for (int d = 0; d < 3; ++d) ro.max_abs_coord[d] = 0.0;
   for (size_t i = 0; i < nodes.size(); ++i) ro.max_abs_coord[i % dim_] = std::max(ro.max_abs_coord[i % dim_], std::fabs(nodes[i]));
-  int max_row = 0;
-  for (int r = 0; r < nrows_; ++r) max_row = std::max(max_row, h_rowptr_[r + 1] - h_rowptr_[r]);
-  MHA_REQUIRE(max_row <= 65536, MHA_ERR_INVALID, "CRS rows longer than 65536 entries are not supported");
-  ro.slot_bytes = max_row <= 256 ? 1 : 2;
+  MHA_REQUIRE(max_row_ <= 65536, MHA_ERR_INVALID, "CRS rows longer than 65536 entries are not supported");
+  ro.slot_bytes = max_row_ <= 256 ? 1 : 2;
   RowBlockCaps caps = default_caps(dim_, n_);
-  // LDS budget: two workgroups per CU (80 KiB each).  An aligned interior chunk touches 3^dim elements
-  // and owns (2*order)^dim rows; the accumulator gets whatever the fixed parts leave.
   {
     // LDS budget of K2: four workgroups per CU (40 KiB each).  An aligned interior chunk touches
     // 3^dim elements; the accumulator gets whatever the pair tables leave.
@@ -1974,30 +1839,13 @@ void AssemblyManager::prepareRowOwner() {
     probe.lds_acc = 0;
     const long fixed_bytes = static_cast<long>(row_owner_jacobian_lds(probe, n_, ro.slot_bytes));
     const long budget = 40 * 1024 - fixed_bytes;
-    MHA_REQUIRE(budget >= 8 * 2 * max_row, MHA_ERR_INVALID, "row-owner kernel does not fit the LDS budget for this element");
+    MHA_REQUIRE(budget >= 8 * 2 * max_row_, MHA_ERR_INVALID, "row-owner kernel does not fit the LDS budget for this element");
     caps.max_acc = std::min(65534, static_cast<int>(budget / 8) / 2 * 2);
   }
   ro.rb = build_row_blocks(dim_, nnodes_, nelem_, n_, nrows_, nodes.data(), h_lids_.data(), h_rowptr_.data(), caps,
                            has_fixed_ ? h_fixed_.data() : nullptr, ro.slot_bytes);
   const RowBlocks &rb = ro.rb;
-  ro.row_ptr.upload(rb.row_ptr);
-  ro.rows.upload(rb.rows);
-  ro.row_off.upload(rb.row_off);
-  ro.acc_size.upload(rb.acc_size);
-  ro.elem_ptr.upload(rb.elem_ptr);
-  ro.elems.upload(rb.elems);
-  ro.pair_ptr.upload(rb.pair_ptr);
-  ro.pairs.upload(rb.pairs);
-  ro.pair_off.upload(rb.pair_off);
-  ro.row_base.upload(rb.row_base);
-  ro.row_len.upload(rb.row_len);
-  ro.emask.upload(rb.emask);
-  ro.epbase.upload(rb.epbase);
-  ro.slot_ptr.upload(rb.slot_ptr);
-  ro.seg_ptr.upload(rb.seg_ptr);
-  ro.seg_acc.upload(rb.seg_acc);
-  ro.seg_base.upload(rb.seg_base);
-  ro.seg_len.upload(rb.seg_len);
+  ro.rb_dev.upload(rb);
   ro.geo.resize(static_cast<size_t>(nelem_) * kGeoRec);
   launch_affine_geometry(b, ro.geo.data(), stream_);
   {
@@ -2017,105 +1865,20 @@ void AssemblyManager::prepareRowOwner() {
   ro.num_general_blocks = static_cast<int>(gen.size());
   ro.affine_list.upload(aff);
   ro.general_list.upload(gen);
-  // 4. block-major slot table (position of every contribution inside its CRS row)
+  // 4. block-major slot table (position of every contribution inside its CRS row), K2's element records and lane layout
   ro.slot.resize(std::max<size_t>(16, static_cast<size_t>(rb.slot_ptr.back())));
-  launch_build_block_slots(b, rowBlocksDev(), ro.slot.data(), ro.slot_bytes, stream_);
+  launch_build_block_slots(b, ro.rb_dev.dev(), ro.slot.data(), ro.slot_bytes, stream_);
   ro.erec.resize(std::max<size_t>(8, rb.elems.size() * 8));
-  launch_build_erec(dim_, rowBlocksDev(), ro.geo.data(), ro.erec.data(), static_cast<int>(rb.elems.size()), stream_);
-  // 4b. lane layout of K2: pair up LID slots that are usually owned together by the same (block, element),
-  //     so that a wave-instruction working on two slots side by side is either skipped or mostly busy.
-  {
-    std::vector<double> both(static_cast<size_t>(n_) * n_, 0.0), cnt(n_, 0.0);
-    const size_t stride = std::max<size_t>(1, rb.emask.size() / 200000);  // a sample is plenty
-    for (size_t i = 0; i < rb.emask.size(); i += stride) {
-      const uint32_t m = static_cast<uint32_t>(rb.emask[i]);
-      for (int a = 0; a < n_ && a < 32; ++a) {
-        if (!((m >> a) & 1u)) continue;
-        cnt[a] += 1.0;
-        for (int c = a + 1; c < n_ && c < 32; ++c)
-          if ((m >> c) & 1u) both[static_cast<size_t>(a) * n_ + c] += 1.0;
-      }
-    }
-    std::vector<int> pairs(2 * ((n_ + 1) / 2), -1);
-    std::vector<char> used(n_, 0);
-    for (int r = 0; r < n_ / 2; ++r) {  // greedy matching by Jaccard similarity of ownership
-      int ba = -1, bc = -1;
-      double best = -1.0;
-      for (int a = 0; a < n_; ++a)
-        for (int c = a + 1; c < n_; ++c) {
-          if (used[a] || used[c]) continue;
-          const double uni = cnt[a] + cnt[c] - both[static_cast<size_t>(a) * n_ + c];
-          const double jac = uni > 0.0 ? both[static_cast<size_t>(a) * n_ + c] / uni : 0.0;
-          if (jac > best) { best = jac; ba = a; bc = c; }
-        }
-      pairs[2 * r] = ba;
-      pairs[2 * r + 1] = bc;
-      used[ba] = used[bc] = 1;
-    }
-    if (n_ % 2)
-      for (int a = 0; a < n_; ++a)
-        if (!used[a]) pairs[2 * (n_ / 2)] = a;
-    ro.slot_pair.upload(pairs);
-  }
-  // 5. reference tables of the affine path, in LID-slot space
-  const int nsym = dim_ * (dim_ + 1) / 2;
-  std::vector<double> khat(static_cast<size_t>(nsym + 1) * n_ * n_, 0.0);
-  std::vector<int32_t> offs(n_);
-  d_offsets_.download(offs.data());
-  for (int ib = 0; ib < n_; ++ib)
-    for (int jb = 0; jb < n_; ++jb) {
-      const size_t idx = static_cast<size_t>(offs[ib]) * n_ + offs[jb];
-      int k = 0;
-      for (int a = 0; a < dim_; ++a)
-        for (int c = a; c < dim_; ++c, ++k) {
-          double s = 0.0;
-          for (int q = 0; q < nq_; ++q) {
-            const double *gi = &ref_.grad[(static_cast<size_t>(ib) * nq_ + q) * dim_];
-            const double *gj = &ref_.grad[(static_cast<size_t>(jb) * nq_ + q) * dim_];
-            s += ref_.wts[q] * (a == c ? gi[a] * gj[a] : gi[a] * gj[c] + gi[c] * gj[a]);
-          }
-          khat[static_cast<size_t>(k) * n_ * n_ + idx] = s;
-        }
-      double m = 0.0;
-      for (int q = 0; q < nq_; ++q) m += ref_.wts[q] * ref_.basis[ib * nq_ + q] * ref_.basis[jb * nq_ + q];
-      khat[static_cast<size_t>(nsym) * n_ * n_ + idx] = m;
-    }
-  ro.khat.upload(khat);
-  // thread-per-element K1: 1-D tables by value; the collocation derivative D = Phi'^T Phi^-T (Gauss-Jordan on the
-  // small, well-conditioned point-value matrix)
+  launch_build_erec(dim_, ro.rb_dev.dev(), ro.geo.data(), ro.erec.data(), static_cast<int>(rb.elems.size()), stream_);
+  ro.slot_pair.upload(pair_lid_slots(rb.emask, n_));
+  // 5. reference tables of the affine path, in LID-slot space; the 1-D tables of the thread-per-element K1
+  ro.khat.upload(affine_reference_tables(ref_, h_offsets_.data(), dim_, n_, nq_));
   ro.k1_thread = false;
   if (thermal_affine_residual_supported(dim_, order_, ref_.nq1)) {
-    const int m = order_ + 1;
-    AffineTables1D &t = ro.tab1d;
-    t = AffineTables1D();
-    for (int i = 0; i < m * m; ++i) t.phi[i] = ref_.phi1d[i];
-    for (int q = 0; q < m; ++q) { t.gw[q] = ref_.gauss_wts[q]; t.gp[q] = ref_.gauss_pts[q]; }
-    // inv = Phi^-1 with Phi[i][q] = phi_i(xi_q)
-    std::vector<double> a(ref_.phi1d.begin(), ref_.phi1d.begin() + m * m), inv(m * m, 0.0);
-    for (int i = 0; i < m; ++i) inv[i * m + i] = 1.0;
-    for (int c = 0; c < m; ++c) {
-      int piv = c;
-      for (int r = c + 1; r < m; ++r)
-        if (std::fabs(a[r * m + c]) > std::fabs(a[piv * m + c])) piv = r;
-      for (int k = 0; k < m; ++k) { std::swap(a[c * m + k], a[piv * m + k]); std::swap(inv[c * m + k], inv[piv * m + k]); }
-      const double d = 1.0 / a[c * m + c];
-      for (int k = 0; k < m; ++k) { a[c * m + k] *= d; inv[c * m + k] *= d; }
-      for (int r = 0; r < m; ++r) {
-        if (r == c) continue;
-        const double f = a[r * m + c];
-        for (int k = 0; k < m; ++k) { a[r * m + k] -= f * a[c * m + k]; inv[r * m + k] -= f * inv[c * m + k]; }
-      }
-    }
-    for (int q = 0; q < m; ++q)
-      for (int qp = 0; qp < m; ++qp) {
-        double s = 0.0;
-        for (int i = 0; i < m; ++i) s += ref_.dphi1d[i * m + q] * inv[qp * m + i];
-        t.dcol[q * m + qp] = s;
-      }
-    const char *k1 = std::getenv("MHA_K1");
-    ro.k1_thread = !(k1 && std::string(k1) == "lanes");
+    ro.tab1d = collocation_derivative(ref_, order_);
+    ro.k1_thread = !env_is("MHA_K1", "lanes");
     ro.k1_plan = K1PlanDev();
-    ro.k1_wg = ro.k1_thread && !(k1 && std::string(k1) == "thread");
+    ro.k1_wg = ro.k1_thread && !env_is("MHA_K1", "thread");
   }
   ro.phi.upload(ref_.phi1d);
   ro.dphi.upload(ref_.dphi1d);
@@ -2123,115 +1886,31 @@ void AssemblyManager::prepareRowOwner() {
   ro.gp.upload(ref_.gauss_pts);
   MHA_HIP(hipStreamSynchronize(stream_));
   if (ro.k1_wg) {
-    // Plan of the workgroup-merged K1 (K1PlanDev): the elements in groups of 256, per group the distinct rows its dofs
-    // touch (ascending) and per (element, dof in basis order) the position of its row in that list.
-    constexpr int T = kK1PlanThreads;
+    // 6. plan of the workgroup-merged K1 and the geometry-shape database (row_owner_plan.hpp); MHA_K1_ORDER=natural|morton
+    //    forces an element order
     std::vector<double> geo(static_cast<size_t>(nelem_) * kGeoRec);
     ro.geo.download(geo.data());
-    bool aligned = true;  // every element axis-aligned (J diagonal: the test the kernels make per element)?
-    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
-    for (int e = 0; e < nelem_; ++e) {
-      const double *g = &geo[static_cast<size_t>(e) * kGeoRec];
-      for (int r = 0; r < dim_; ++r) {
-        lo[r] = std::min(lo[r], g[kGeoXc + r]);
-        hi[r] = std::max(hi[r], g[kGeoXc + r]);
-        for (int c = 0; c < dim_; ++c)
-          if (r != c && g[kGeoJ + r * dim_ + c] != 0.0) aligned = false;
-      }
-    }
-    // order of the elements: as numbered (coalesced record loads; good whenever consecutive elements are neighbours),
-    // or along a Morton curve through the centroids when the numbering scatters a group over the mesh (its distinct
-    // rows would not fit the LDS three workgroups deep); MHA_K1_ORDER=natural|morton forces one
-    const char *ord = std::getenv("MHA_K1_ORDER");
-    const int G = (nelem_ + T - 1) / T;
-    std::vector<int32_t> wg_elems(static_cast<size_t>(G) * T), rp, rows, tmp;
-    std::vector<uint16_t> loc;
-    int max_rows = 0;
-    auto build = [&](bool natural) {
-      std::vector<std::pair<uint64_t, int32_t>> keyed(nelem_);
-      for (int e = 0; e < nelem_; ++e) {
-        uint64_t key = 0;
-        if (!natural) {
-          uint32_t q[3] = {0, 0, 0};
-          for (int r = 0; r < dim_; ++r) {
-            const double w = hi[r] > lo[r] ? (geo[static_cast<size_t>(e) * kGeoRec + kGeoXc + r] - lo[r]) / (hi[r] - lo[r]) : 0.0;
-            q[r] = static_cast<uint32_t>(std::min(1048575.0, std::max(0.0, w * 1048575.0)));
-          }
-          for (int bit = 19; bit >= 0; --bit)
-            for (int r = dim_ - 1; r >= 0; --r) key = (key << 1) | ((q[r] >> bit) & 1u);
-        }
-        keyed[e] = {key, e};
-      }
-      std::sort(keyed.begin(), keyed.end());
-      for (size_t i = 0; i < wg_elems.size(); ++i) wg_elems[i] = keyed[std::min<size_t>(i, nelem_ - 1)].second;
-      rp.assign(static_cast<size_t>(G) + 1, 0);
-      rows.clear();
-      rows.reserve(static_cast<size_t>(nelem_) * n_ / 2);
-      loc.assign(static_cast<size_t>(G) * n_ * T, 0);
-      max_rows = 0;
-      for (int g = 0; g < G; ++g) {
-        const int cnt = std::min(T, nelem_ - g * T);
-        tmp.clear();
-        for (int t = 0; t < cnt; ++t) {
-          const int32_t *L = &h_lids_[static_cast<size_t>(wg_elems[static_cast<size_t>(g) * T + t]) * n_];
-          tmp.insert(tmp.end(), L, L + n_);
-        }
-        std::sort(tmp.begin(), tmp.end());
-        tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-        for (int t = 0; t < cnt; ++t) {
-          const int32_t *L = &h_lids_[static_cast<size_t>(wg_elems[static_cast<size_t>(g) * T + t]) * n_];
-          for (int ib = 0; ib < n_; ++ib)
-            loc[(static_cast<size_t>(g) * n_ + ib) * T + t] =
-                static_cast<uint16_t>(std::lower_bound(tmp.begin(), tmp.end(), L[offs[ib]]) - tmp.begin());
-        }
-        rows.insert(rows.end(), tmp.begin(), tmp.end());
-        rp[g + 1] = static_cast<int32_t>(rows.size());
-        max_rows = std::max(max_rows, static_cast<int>(tmp.size()));
-      }
-    };
-    const bool force_morton = ord && std::string(ord) == "morton", force_natural = ord && std::string(ord) == "natural";
-    build(!force_morton);
-    if (!force_morton && !force_natural && static_cast<size_t>(max_rows) * 12 > 52 * 1024) {
-      const int natural_rows = max_rows;
-      build(false);
-      if (max_rows >= natural_rows) build(true);
-    }
-    ro.k1_row_ptr.upload(rp);
-    ro.k1_rows.upload(rows);
-    ro.k1_loc.upload(loc);
-    ro.k1_elems.upload(wg_elems);
+    const K1Order forced = env_is("MHA_K1_ORDER", "morton") ? K1Order::morton
+                           : env_is("MHA_K1_ORDER", "natural") ? K1Order::natural : K1Order::automatic;
+    const K1Plan kp = build_k1_plan(nelem_, n_, dim_, h_lids_.data(), h_offsets_.data(), geo.data(), forced);
+    ro.k1_row_ptr.upload(kp.row_ptr);
+    ro.k1_rows.upload(kp.rows);
+    ro.k1_loc.upload(kp.loc);
+    ro.k1_elems.upload(kp.wg_elems);
     ro.k1_plan.wg_row_ptr = ro.k1_row_ptr.data();
     ro.k1_plan.wg_rows = ro.k1_rows.data();
     ro.k1_plan.loc = ro.k1_loc.data();
     ro.k1_plan.wg_elems = ro.k1_elems.data();
-    ro.k1_plan.max_rows = (max_rows + 1) / 2 * 2;
+    ro.k1_plan.max_rows = kp.max_rows;
     ro.k1_plan.num_elems = nelem_;
-    ro.k1_plan.axis_aligned = aligned ? 1 : 0;
-    // geometry database (reference: identifyVolumetricDatabase, assemblyManager.cpp:4314-4467; here exact matching of
-    // the 16 shape doubles, bit for bit, so nothing is substituted): distinct shapes in order of first appearance
-    {
-      static_assert(kGeoXc == 16, "the shape part of a geometry record is its first 16 doubles");
-      std::unordered_map<std::string, int32_t> seen;
-      std::vector<double> shapes;
-      std::vector<int32_t> sidx(nelem_);
-      const int nsym_g = dim_ * (dim_ + 1) / 2;
-      for (int e = 0; e < nelem_; ++e) {
-        double rec[16];
-        for (int k = 0; k < 16; ++k) {  // (entries a 2-D record does not use are not part of the shape)
-          const bool used = k < nsym_g || k == kGeoDet || (k >= kGeoJ && k < kGeoJ + dim_ * dim_);
-          rec[k] = used ? geo[static_cast<size_t>(e) * kGeoRec + k] : 0.0;
-        }
-        auto it = seen.emplace(std::string(reinterpret_cast<const char *>(rec), sizeof(rec)), static_cast<int32_t>(seen.size()));
-        if (it.second) shapes.insert(shapes.end(), rec, rec + 16);
-        sidx[e] = it.first->second;
-      }
-      ro.k1_shape.upload(shapes);
-      ro.k1_shape_idx.upload(sidx);
-      ro.k1_plan.shape = ro.k1_shape.data();
-      ro.k1_plan.shape_idx = ro.k1_shape_idx.data();
-      ro.k1_plan.num_shapes = static_cast<int>(seen.size());
-      ro.num_shapes = ro.k1_plan.num_shapes;
-    }
+    ro.k1_plan.axis_aligned = kp.axis_aligned ? 1 : 0;
+    const ShapeTable st = distinct_shapes(geo.data(), nelem_, dim_);
+    ro.k1_shape.upload(st.shapes);
+    ro.k1_shape_idx.upload(st.index);
+    ro.k1_plan.shape = ro.k1_shape.data();
+    ro.k1_plan.shape_idx = ro.k1_shape_idx.data();
+    ro.k1_plan.num_shapes = st.count;
+    ro.num_shapes = st.count;
   }
   ro.ready = true;
   prepareBlockPattern();
@@ -2244,8 +1923,7 @@ void AssemblyManager::prepareBlockPattern() {
   bp.tried = true;
   bp.usable = false;
   ++bpat_generation_;  // whatever is rebuilt below, kept representatives were made from the tables before it
-  const char *mode = std::getenv("MHA_K2");
-  if (mode && std::string(mode) == "blocks") { bp.why = "row-block kernel requested (MHA_K2=blocks)"; return; }
+  if (env_is("MHA_K2", "blocks")) { bp.why = "row-block kernel requested (MHA_K2=blocks)"; return; }
   if (ro_.num_general_blocks > 0) { bp.why = "block has non-affine elements"; return; }
   if (static_cast<long long>(h_rowptr_[nrows_]) >= (1ll << 28)) { bp.why = "more than 2^28 CRS entries (32-bit byte offsets)"; return; }
   // its own partition: larger Morton chunks (16 elements = 16 rows of every class of a Q2 hex block: whole MFMA panels),
@@ -2256,8 +1934,7 @@ void AssemblyManager::prepareBlockPattern() {
   caps.max_elems = 255;
   caps.max_pairs = 1 << 20;
   caps.max_acc = 1 << 30;
-  std::vector<double> nodes(static_cast<size_t>(nelem_) * nnodes_ * dim_);
-  d_nodes_.download(nodes.data());
+  const std::vector<double> nodes = hostNodes();
   RowBlocks rb;
   try {
     rb = build_row_blocks(dim_, nnodes_, nelem_, n_, nrows_, nodes.data(), h_lids_.data(), h_rowptr_.data(), caps,
@@ -2266,7 +1943,6 @@ void AssemblyManager::prepareBlockPattern() {
     bp.why = e.what();
     return;
   }
-  if (static_cast<int>(rb.rows.size()) != nrows_ && !ro_.all_rows_covered) { /* rows without elements stay untouched on both paths */ }
   prepareElemSlots();
   std::vector<uint8_t> slot(static_cast<size_t>(nelem_) * n_ * n_ * elem_slot_bytes_);
   MHA_HIP(hipStreamSynchronize(stream_));
@@ -2358,7 +2034,7 @@ void AssemblyManager::prepareBlockPattern() {
 bool AssemblyManager::rowOwnerUsable(std::string *why) const {
   auto fail = [&](const char *m) { if (why) *why = m; return false; };
   if (!ro_.ready) return fail("partition not built (unsupported element?)");
-  if (ro_.num_general_blocks > 0) return fail("block has non-affine elements (general row-owner kernel not built yet)");
+  if (ro_.num_general_blocks > 0) return fail("block has non-affine elements: the affine kernels do not apply");
   for (const char *name : {"thermal diffusion", "specific heat", "density"})
     if (functions_.evaluate(name).kind != MHA_FUNC_CONSTANT) return fail("coefficient is not element-wise constant");
   return true;
@@ -2367,30 +2043,6 @@ bool AssemblyManager::rowOwnerUsable(std::string *why) const {
 // ---------------------------------------------------------------------------------------------
 // general-element row-owner kernel
 // ---------------------------------------------------------------------------------------------
-
-RowBlocksDev AssemblyManager::generalRowBlocksDev() const {
-  RowBlocksDev rb;
-  rb.num_blocks = gro_.rb.num_blocks;
-  rb.row_ptr = gro_.row_ptr.data();
-  rb.rows = gro_.rows.data();
-  rb.elem_ptr = gro_.elem_ptr.data();
-  rb.elems = gro_.elems.data();
-  rb.pair_ptr = gro_.pair_ptr.data();
-  rb.pairs = gro_.pairs.data();
-  rb.pair_off = gro_.pair_off.data();
-  rb.row_len = gro_.row_len.data();
-  rb.slot_ptr = gro_.slot_ptr.data();
-  rb.seg_ptr = gro_.seg_ptr.data();
-  rb.seg_acc = gro_.seg_acc.data();
-  rb.seg_base = gro_.seg_base.data();
-  rb.seg_len = gro_.seg_len.data();
-  rb.lds_rows = gro_.rb.max_rows;
-  rb.lds_elems = gro_.rb.max_elems;
-  rb.lds_acc = gro_.rb.max_acc;
-  rb.lds_pairs = gro_.rb.max_pairs;
-  rb.lds_segs = gro_.rb.max_segs;
-  return rb;
-}
 
 // Row blocks for the general row-owner kernel: Morton chunks of 2x2x2 (4x4) elements, at most 27 (25) touched elements,
 // 256 pairs (16 matrix-core tiles) and an accumulator that leaves room for the per-element point data in LDS.  Any
@@ -2402,16 +2054,13 @@ void AssemblyManager::prepareGeneralRowOwner() {
   auto fail = [&](const std::string &m) { gro_.why = m; gro_.usable = false; };
   if (!single_hgrad_ || !thermal_general_row_owner_supported(dim_, order_, ref_.nq1))
     return fail("unsupported (dim, order, points/dir) for the general row-owner kernel");
-  int max_row = 0;
-  for (int r = 0; r < nrows_; ++r) max_row = std::max(max_row, h_rowptr_[r + 1] - h_rowptr_[r]);
-  if (max_row > 256) return fail("CRS rows longer than 256 entries");
+  if (max_row_ > 256) return fail("CRS rows longer than 256 entries");
   RowBlockCaps caps = default_caps(dim_, n_);
   caps.max_elems = (dim_ == 3) ? 27 : 25;
   caps.max_rows = 128;
   caps.max_pairs = 256;
   caps.max_acc = 4352;
-  std::vector<double> nodes(static_cast<size_t>(nelem_) * nnodes_ * dim_);
-  d_nodes_.download(nodes.data());
+  const std::vector<double> nodes = hostNodes();
   try {
     gro_.rb = build_row_blocks(dim_, nnodes_, nelem_, n_, nrows_, nodes.data(), h_lids_.data(), h_rowptr_.data(), caps,
                                has_fixed_ ? h_fixed_.data() : nullptr, 1);
@@ -2419,29 +2068,16 @@ void AssemblyManager::prepareGeneralRowOwner() {
     return fail(e.what());
   }
   const RowBlocks &rb = gro_.rb;
-  gro_.row_ptr.upload(rb.row_ptr);
-  gro_.rows.upload(rb.rows);
-  gro_.elem_ptr.upload(rb.elem_ptr);
-  gro_.elems.upload(rb.elems);
-  gro_.pair_ptr.upload(rb.pair_ptr);
-  gro_.pairs.upload(rb.pairs);
-  gro_.pair_off.upload(rb.pair_off);
-  gro_.row_len.upload(rb.row_len);
-  gro_.slot_ptr.upload(rb.slot_ptr);
-  gro_.seg_ptr.upload(rb.seg_ptr);
-  gro_.seg_acc.upload(rb.seg_acc);
-  gro_.seg_base.upload(rb.seg_base);
-  gro_.seg_len.upload(rb.seg_len);
+  gro_.rb_dev.upload(rb, false);
   gro_.all_rows_covered = static_cast<int>(rb.rows.size()) == nrows_;
-  gro_.lds_bytes = thermal_general_row_owner_lds(dim_, order_, ref_.nq1, generalRowBlocksDev());
+  gro_.lds_bytes = thermal_general_row_owner_lds(dim_, order_, ref_.nq1, gro_.rb_dev.dev());
   if (gro_.lds_bytes > size_t(160) * 1024) return fail("row blocks do not fit the LDS of the general row-owner kernel");
   gro_.slot.resize(std::max<size_t>(16, static_cast<size_t>(rb.slot_ptr.back())));
-  launch_build_block_slots(blockDev(), generalRowBlocksDev(), gro_.slot.data(), 1, stream_);
+  launch_build_block_slots(blockDev(), gro_.rb_dev.dev(), gro_.slot.data(), 1, stream_);
   {  // block-major row ids of the touched elements' dofs (dof order): the kernel's gather is then two loads deep
-    std::vector<int32_t> offs(n_), br(rb.elems.size() * static_cast<size_t>(n_));
-    d_offsets_.download(offs.data());
+    std::vector<int32_t> br(rb.elems.size() * static_cast<size_t>(n_));
     for (size_t k = 0; k < rb.elems.size(); ++k)
-      for (int j = 0; j < n_; ++j) br[k * n_ + j] = h_lids_[static_cast<size_t>(rb.elems[k]) * n_ + offs[j]];
+      for (int j = 0; j < n_; ++j) br[k * n_ + j] = h_lids_[static_cast<size_t>(rb.elems[k]) * n_ + h_offsets_[j]];
     gro_.blk_rows.upload(br);
     // block headers, 12 ints each: first touched element, T, first pair, NP, first row, NR, first run, NS,
     // slot-table offset / 16, slot-table uint4s
@@ -2473,41 +2109,12 @@ void AssemblyManager::launchGeneralRowOwner(bool compute_jacobian, bool overwrit
   out.compute_jacobian = compute_jacobian ? 1 : 0;
   out.ordered = ordered ? 1 : 0;
   MHA_REQUIRE(!ordered || !compute_jacobian, MHA_ERR_INVALID, "the ordered residual sums exist in the residual-only pass");
-  launch_thermal_general_row_owner(dim_, order_, ref_.nq1, blockDev(), ph, generalRowBlocksDev(), gro_.slot.data(),
+  launch_thermal_general_row_owner(dim_, order_, ref_.nq1, blockDev(), ph, gro_.rb_dev.dev(), gro_.slot.data(),
                                    gro_.blk_rows.data(), d_gp1d_.data(), gro_.blk_hdr.data(), out, current_device_num_cus(), stream_);
 }
 
-RowBlocksDev AssemblyManager::rowBlocksDev() const {
-  RowBlocksDev rb;
-  rb.num_blocks = ro_.rb.num_blocks;
-  rb.row_ptr = ro_.row_ptr.data();
-  rb.rows = ro_.rows.data();
-  rb.row_off = ro_.row_off.data();
-  rb.acc_size = ro_.acc_size.data();
-  rb.elem_ptr = ro_.elem_ptr.data();
-  rb.elems = ro_.elems.data();
-  rb.pair_ptr = ro_.pair_ptr.data();
-  rb.pairs = ro_.pairs.data();
-  rb.pair_off = ro_.pair_off.data();
-  rb.row_base = ro_.row_base.data();
-  rb.row_len = ro_.row_len.data();
-  rb.emask = ro_.emask.data();
-  rb.epbase = ro_.epbase.data();
-  rb.slot_ptr = ro_.slot_ptr.data();
-  rb.seg_ptr = ro_.seg_ptr.data();
-  rb.seg_acc = ro_.seg_acc.data();
-  rb.seg_base = ro_.seg_base.data();
-  rb.seg_len = ro_.seg_len.data();
-  rb.lds_rows = ro_.rb.max_rows;
-  rb.lds_elems = ro_.rb.max_elems;
-  rb.lds_acc = ro_.rb.max_acc;
-  rb.lds_pairs = ro_.rb.max_pairs;
-  rb.lds_segs = ro_.rb.max_segs;
-  return rb;
-}
-
 void AssemblyManager::launchRowOwner(bool compute_jacobian, bool overwrite, double *res, double *crs_vals, bool deterministic) {
-  const RowBlocksDev rb = rowBlocksDev();
+  const RowBlocksDev rb = ro_.rb_dev.dev();
   AffineDev af;
   af.khat = ro_.khat.data();
   af.phi1d = ro_.phi.data();
@@ -2623,7 +2230,7 @@ int64_t AssemblyManager::info(const std::string &key) const {
   if (key == "row_block_max_acc") return ro_.rb.max_acc;
   if (key == "row_block_max_pairs") return ro_.rb.max_pairs;
   if (key == "row_owner_lds_bytes")
-    return ro_.ready ? static_cast<int64_t>(row_owner_jacobian_lds(rowBlocksDev(), n_, ro_.slot_bytes)) : 0;
+    return ro_.ready ? static_cast<int64_t>(row_owner_jacobian_lds(ro_.rb_dev.dev(), n_, ro_.slot_bytes)) : 0;
   throw Error(MHA_ERR_INVALID, "unknown info key '" + key + "'");
 }
 

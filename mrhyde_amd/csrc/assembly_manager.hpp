@@ -13,7 +13,8 @@
 #include "common.hpp"
 #include "physics.hpp"
 #include "ref_tables.hpp"
-#include "row_blocks.hpp"
+#include "mesh.hpp"
+#include "row_blocks_device.hpp"
 #include "block_pattern.hpp"
 #include "workset.hpp"
 
@@ -123,7 +124,6 @@ class AssemblyManager {
   void tryPrepareRowOwner();
   bool rowOwnerUsable(std::string *why) const;
   void launchRowOwner(bool compute_jacobian, bool overwrite, double *res, double *crs_vals, bool deterministic = false);
-  RowBlocksDev rowBlocksDev() const;
   BlockDev blockDev() const;
   void bindState(const double *u, const double *u_prev, const double *u_stage);
   void timedBegin();
@@ -175,7 +175,9 @@ class AssemblyManager {
   bool porousDatabaseUsable();
   void launchDatabaseCopy(double *crs_vals);
   bool has_incidence_ = false;
-  int max_row_ = 0;
+  RowIncidence inc_;  // host copy, shared by the row gather and the two porousMixed plans
+  const RowIncidence &rowIncidence();
+  int max_row_ = 0;  // longest CRS row (setGraph)
   void prepareRowGather(bool need_jacobian, bool dense = true);
   void launchPointEngine(int compute_jacobian, const ElemOut &out, int e_begin, int e_count);
   int nelem_ = 0, nrows_ = 0, workset_size_ = 0;
@@ -198,6 +200,8 @@ class AssemblyManager {
   DeviceBuffer<int32_t> d_lids_, d_offsets_, d_rowptr_, d_colind_;
   DeviceBuffer<uint8_t> d_fixed_;
   std::vector<int32_t> h_lids_, h_rowptr_, h_colind_;
+  std::vector<int32_t> h_offsets_, h_p2d_;  // LID position of every dof, and its inverse
+  std::vector<double> hostNodes() const;    // downloaded on demand: [E][nnodes][dim]
   std::vector<uint8_t> h_fixed_;
   bool has_fixed_ = false;
 
@@ -206,14 +210,12 @@ class AssemblyManager {
     bool ready = false;
     bool failed = false;  // prepareRowOwner threw: AUTO stops trying
     RowBlocks rb;
-    DeviceBuffer<int32_t> row_ptr, rows, row_off, acc_size, elem_ptr, elems, pair_ptr, affine_list, general_list;
-    DeviceBuffer<int32_t> pair_off, row_base, row_len, emask, epbase, seg_ptr, seg_acc, seg_base, seg_len;
-    DeviceBuffer<int64_t> slot_ptr;
+    RowBlocksOnDevice rb_dev;
+    DeviceBuffer<int32_t> affine_list, general_list;
     DeviceBuffer<double> geo;  // [E][kGeoRec] cached element geometry
     DeviceBuffer<double> erec;  // block-major element records of K2
     DeviceBuffer<uint16_t> pair_off16;
     DeviceBuffer<int> slot_pair;  // LID slots paired by co-ownership (K2 lane layout)
-    DeviceBuffer<uint32_t> pairs;
     DeviceBuffer<uint8_t> slot, flags;
     DeviceBuffer<double> khat, phi, dphi, gw, gp;
     AffineTables1D tab1d;  // thread-per-element K1
@@ -236,17 +238,14 @@ class AssemblyManager {
     bool tried = false, usable = false;
     std::string why;
     RowBlocks rb;
-    DeviceBuffer<int32_t> row_ptr, rows, elem_ptr, elems, pair_ptr, pair_off, row_len, seg_ptr, seg_acc, seg_base, seg_len;
+    RowBlocksOnDevice rb_dev;  // without the accumulator tables, which this kernel does not read
     DeviceBuffer<int32_t> blk_rows;  // [touched element of every block][n]: global row of dof j
     DeviceBuffer<int32_t> blk_hdr;   // [block][12] counts and offsets of the block's tables
-    DeviceBuffer<int64_t> slot_ptr;
-    DeviceBuffer<uint32_t> pairs;
     DeviceBuffer<uint8_t> slot;
     bool all_rows_covered = false;
     size_t lds_bytes = 0;
   } gro_;
   void prepareGeneralRowOwner();
-  RowBlocksDev generalRowBlocksDev() const;
   void launchGeneralRowOwner(bool compute_jacobian, bool overwrite, double *res, double *crs_vals, bool ordered = false);
   // row blocks keyed by assembly pattern: the matrix-core form of K2 (block_pattern.hpp); !usable -> the row-block kernel
   // inputs of the geometry-database representatives: the bits of su = alpha_u * kappa and st = alpha_t * rho * c_p,

@@ -13,6 +13,8 @@
 #include "block_pattern.hpp"
 #include "newton.hpp"
 #include "porous_data.hpp"
+#include "porous_plan.hpp"
+#include "row_owner_plan.hpp"
 #include "test_hooks.h"
 #include "scatter_plan.hpp"
 #include "export_plan.hpp"
@@ -917,6 +919,93 @@ int mha_test_block_pattern_step_plan(int dim, int num_rows, int num_elems, int n
     std::copy(cp.seg.begin(), cp.seg.begin() + 2 * counts[1], segs);
     std::copy(cp.item.begin(), cp.item.end(), items);
     mha::copy_plan_host_apply(cp, vals_db, stores, rep_vals.data());
+  });
+}
+
+int mha_test_k1_plan(int num_elems, int n, int dim, const int32_t *lids, const int32_t *offsets, const double *geo, int order,
+                     int row_budget, int32_t *wg_elems, int32_t *row_ptr, int32_t *rows, uint16_t *loc, int *counts) {
+  return guarded([&] {
+    MHA_REQUIRE(lids && offsets && geo && wg_elems && row_ptr && rows && loc && counts && order >= 0 && order <= 2,
+                MHA_ERR_INVALID, "bad argument");
+    const mha::K1Plan p = mha::build_k1_plan(num_elems, n, dim, lids, offsets, geo, static_cast<mha::K1Order>(order),
+                                             row_budget > 0 ? row_budget : mha::kK1RowBudget);
+    std::copy(p.wg_elems.begin(), p.wg_elems.end(), wg_elems);
+    std::copy(p.row_ptr.begin(), p.row_ptr.end(), row_ptr);
+    std::copy(p.rows.begin(), p.rows.end(), rows);
+    std::copy(p.loc.begin(), p.loc.end(), loc);
+    counts[0] = static_cast<int>(p.rows.size());
+    counts[1] = p.max_rows;
+    counts[2] = p.axis_aligned;
+    counts[3] = p.morton;
+  });
+}
+
+int mha_test_distinct_shapes(const double *geo, int num_elems, int dim, double *shapes, int32_t *index, int *count) {
+  return guarded([&] {
+    MHA_REQUIRE(geo && shapes && index && count, MHA_ERR_INVALID, "null argument");
+    const mha::ShapeTable st = mha::distinct_shapes(geo, num_elems, dim);
+    std::copy(st.shapes.begin(), st.shapes.end(), shapes);
+    std::copy(st.index.begin(), st.index.end(), index);
+    *count = st.count;
+  });
+}
+
+int mha_test_pair_lid_slots(const int32_t *emask, int64_t len, int n, int32_t *pairs) {
+  return guarded([&] {
+    MHA_REQUIRE(emask && pairs && n >= 1, MHA_ERR_INVALID, "bad argument");
+    const std::vector<int> p = mha::pair_lid_slots(std::vector<int32_t>(emask, emask + len), n);
+    std::copy(p.begin(), p.end(), pairs);
+  });
+}
+
+int mha_test_collocation_derivative(int order, double *dcol, double *phi, double *dphi) {
+  return guarded([&] {
+    MHA_REQUIRE(order >= 1 && order <= 4 && dcol && phi && dphi, MHA_ERR_INVALID, "bad argument");
+    const mha::RefTables ref = mha::make_ref_tables(2, order, 2 * order);
+    const int m = order + 1;
+    MHA_REQUIRE(ref.nq1 == m, MHA_ERR_INVALID, "the rule has " << ref.nq1 << " points per direction");
+    const mha::AffineTables1D t = mha::collocation_derivative(ref, order);
+    std::copy(t.dcol, t.dcol + m * m, dcol);
+    std::copy(ref.phi1d.begin(), ref.phi1d.begin() + m * m, phi);
+    std::copy(ref.dphi1d.begin(), ref.dphi1d.begin() + m * m, dphi);
+  });
+}
+
+int mha_test_porous_direct_plan(int num_rows, int num_elems, int n, const int32_t *lids, const int32_t *offsets,
+                                const int32_t *rowptr, const int32_t *colind, uint8_t *side, int32_t *diag) {
+  return guarded([&] {
+    MHA_REQUIRE(lids && offsets && rowptr && colind && side && diag, MHA_ERR_INVALID, "null argument");
+    mha::RowIncidence inc;
+    mha::build_row_incidence(num_rows, num_elems, n, lids, inc.ptr, inc.elem, inc.lpos);
+    const mha::PorousDirectPlan p = mha::porous_direct_plan(num_rows, num_elems, n, lids, offsets, rowptr, colind, inc);
+    MHA_REQUIRE(p.usable, MHA_ERR_INVALID, p.why);
+    std::copy(p.side.begin(), p.side.end(), side);
+    std::copy(p.diag.begin(), p.diag.end(), diag);
+  });
+}
+
+int mha_test_porous_database_plan(int num_rows, int num_elems, int n, int nnodes, int dim, const int32_t *lids,
+                                  const int32_t *offsets, const int32_t *rowptr, const int32_t *colind, const double *nodes,
+                                  const int8_t *orient, const uint8_t *fixed, const uint8_t *slot, uint8_t *jacflag,
+                                  int32_t *elist, int32_t *diag, int64_t *runs, int64_t runs_len, int64_t *counts) {
+  return guarded([&] {
+    MHA_REQUIRE(lids && offsets && rowptr && colind && nodes && slot && jacflag && elist && diag && runs && counts,
+                MHA_ERR_INVALID, "null argument");
+    mha::RowIncidence inc;
+    mha::build_row_incidence(num_rows, num_elems, n, lids, inc.ptr, inc.elem, inc.lpos);
+    const mha::PorousDatabasePlan p = mha::porous_database_plan(num_rows, num_elems, n, nnodes, dim, offsets, rowptr, colind,
+                                                                nodes, orient, fixed, slot, inc);
+    MHA_REQUIRE(p.usable, MHA_ERR_INVALID, p.why);
+    MHA_REQUIRE(runs_len >= 3 * static_cast<int64_t>(p.runs.size()), MHA_ERR_INVALID, "run array too short");
+    std::copy(p.jacflag.begin(), p.jacflag.end(), jacflag);
+    std::copy(p.elist.begin(), p.elist.end(), elist);
+    std::copy(p.diag.begin(), p.diag.end(), diag);
+    for (size_t i = 0; i < p.runs.size(); ++i) { runs[3 * i] = p.runs[i].src; runs[3 * i + 1] = p.runs[i].dst; runs[3 * i + 2] = p.runs[i].len; }
+    counts[0] = p.axis_aligned;
+    counts[1] = static_cast<int64_t>(p.elist.size());
+    counts[2] = static_cast<int64_t>(p.runs.size());
+    counts[3] = p.num_classes;
+    counts[4] = p.computed_rows;
   });
 }
 

@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstdint>
+#include <cstring>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -128,6 +129,12 @@ inline void require_modest_scratch(Kernel kern, const char *what) {
   MHA_REQUIRE(attr.localSizeBytes <= limit, MHA_ERR_DEVICE,
               what << ": the kernel needs " << attr.localSizeBytes << " B of scratch per lane (limit " << limit
                    << "): refusing a launch the runtime may not be able to back");
+}
+
+// environment variable `name` is set to exactly `value`
+inline bool env_is(const char *name, const char *value) {
+  const char *v = std::getenv(name);
+  return v && std::strcmp(v, value) == 0;
 }
 
 inline int ipow(int b, int e) { int r = 1; while (e-- > 0) r *= b; return r; }

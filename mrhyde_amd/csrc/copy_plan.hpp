@@ -1,7 +1,7 @@
 // copy_plan.hpp -- the line-aligned copy plan of the database modes (kernels/line_copy.hip).
 //
 // Both database modes (thermal geometry database: AssemblyManager::prepareBlockPattern; porousMixed row classes:
-// AssemblyManager::porousDatabaseUsable) compute a few representative CRS entries and copy them into the rest of the
+// porous_plan.hpp) compute a few representative CRS entries and copy them into the rest of the
 // value array.  The caller describes the copy as RUNS (source entry, destination entry, length) inside vals[0, nnz);
 // every entry no run covers is IN PLACE: written earlier on the same stream, left as it is.
 //

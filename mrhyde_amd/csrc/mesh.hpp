@@ -46,6 +46,7 @@ void build_crs_graph(int nrows, int nelem, int n, const int32_t *lids, std::vect
 void validate_crs_graph(int nrows, int nelem, int n, const int32_t *lids, const int32_t *rowptr, const int32_t *colind);
 
 // row -> incident (element, local position) pairs, CSR layout, element-ascending per row.
+struct RowIncidence { std::vector<int32_t> ptr, elem, lpos; };
 void build_row_incidence(int nrows, int nelem, int n, const int32_t *lids, std::vector<int32_t> &ptr,
                          std::vector<int32_t> &elem, std::vector<int32_t> &lpos);
 

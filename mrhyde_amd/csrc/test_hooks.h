@@ -74,6 +74,32 @@ int mha_test_block_pattern_step_plan(int dim, int num_rows, int num_elems, int n
 int mha_test_swhdg_check_subgrids(int m, int num_elems, int num_rows, const double *nodes, const int32_t *lids,
                                   const int32_t *offsets);
 
+/* The host-side plans of the affine row-owner path (csrc/row_owner_plan.hpp).  Stateless.
+ * K1 plan of geo [num_elems][20] geometry records: order 0 automatic / 1 natural / 2 morton, row_budget <= 0: the default.
+ * wg_elems [groups*256], row_ptr [groups+1], rows [<= num_elems*n], loc [groups*n*256], groups = ceil(num_elems / 256);
+ * counts[4] = {distinct rows in all, max_rows, axis_aligned, morton order taken}. */
+int mha_test_k1_plan(int num_elems, int n, int dim, const int32_t *lids, const int32_t *offsets, const double *geo, int order,
+                     int row_budget, int32_t *wg_elems, int32_t *row_ptr, int32_t *rows, uint16_t *loc, int *counts);
+/* shapes [num_elems][16] (the first *count records are filled), index [num_elems] */
+int mha_test_distinct_shapes(const double *geo, int num_elems, int dim, double *shapes, int32_t *index, int *count);
+/* pairs [2*ceil(n/2)] from the ownership masks emask [len] */
+int mha_test_pair_lid_slots(const int32_t *emask, int64_t len, int n, int32_t *pairs);
+/* the 1-D tables of the HGRAD basis of `order` at order + 1 Gauss points: dcol, phi, dphi [order+1][order+1] */
+int mha_test_collocation_derivative(int order, double *dcol, double *phi, double *dphi);
+
+/* The host-side plans of the porousMixed direct form and its database mode (csrc/porous_plan.hpp) on host arrays in
+ * mha_set_mesh / mha_set_graph form.  A mesh the plan refuses gives MHA_ERR_INVALID with the reason.  Stateless.
+ * side [num_elems][n], diag [num_rows]. */
+int mha_test_porous_direct_plan(int num_rows, int num_elems, int n, const int32_t *lids, const int32_t *offsets,
+                                const int32_t *rowptr, const int32_t *colind, uint8_t *side, int32_t *diag);
+/* orient [num_elems][n] or NULL, fixed [num_rows] or NULL, slot [num_elems][n][n]: position of column lids[e][j] in row
+ * lids[e][i].  jacflag, elist [num_elems], diag [num_rows], runs [runs_len >= 3 x copy runs] = (source entry, destination
+ * entry, length); counts[5] = {axis_aligned, listed elements, copy runs, row classes, computed rows}. */
+int mha_test_porous_database_plan(int num_rows, int num_elems, int n, int nnodes, int dim, const int32_t *lids,
+                                  const int32_t *offsets, const int32_t *rowptr, const int32_t *colind, const double *nodes,
+                                  const int8_t *orient, const uint8_t *fixed, const uint8_t *slot, uint8_t *jacflag,
+                                  int32_t *elist, int32_t *diag, int64_t *runs, int64_t runs_len, int64_t *counts);
+
 #ifdef __cplusplus
 }
 #endif
