@@ -905,27 +905,42 @@ void AssemblyManager::getMass(const double *masswts, double *local_mass) {
   MHA_HIP(hipStreamSynchronize(stream_));  // zero_u is released on return
 }
 
-// HDG element of shallowwaterHybridized, side part (kernels/swhdg_element.hip): residual and derivative blocks of the
-// interior + trace unknowns; settings g / stabilisation from the module
-void AssemblyManager::swhdgElementBlocks(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
-                                         const uint8_t *side_types, const double *farfield, double *res, double *blocks) {
+// What the four HDG element steps of shallowwaterHybridized share: the module and (need_layout) the subgrid layout are
+// checked, the state is bound, the side tables are made, and the kernels' arguments are filled -- traces, side types,
+// far field, g / stabilisation from the module, the three source functions.  The caller adds its outputs to `a`.
+AssemblyManager::SwhStep AssemblyManager::swhStepArgs(const double *u, const double *u_prev, const double *u_stage,
+                                                      const double *lambda, const uint8_t *side_types, const double *farfield,
+                                                      bool need_layout) {
   requireReady(false);
   shallowwaterHybridized *sw = dynamic_cast<shallowwaterHybridized *>(physics_.get());
   MHA_REQUIRE(sw != nullptr, MHA_ERR_INVALID, "the block's physics module is not shallowwaterHybridized");
-  MHA_REQUIRE(lambda && (res || blocks), MHA_ERR_INVALID, "null trace values or outputs");
-  for (const auto &vi : vars_) MHA_REQUIRE(vi.order == 1, MHA_ERR_INVALID, "the HDG element is built for order-1 variables");
+  MHA_REQUIRE(!need_layout || subgrid_m_ > 0, MHA_ERR_STATE, "no subgrid layout: call mha_swhdg_set_subgrids first");
   bindState(u, u_prev, u_stage);
   prepareSideTables();
-  SwhElementDev a;
-  a.lambda = lambda;
-  a.side_types = side_types;
-  if (farfield) for (int i = 0; i < 3; ++i) a.farfield[i] = farfield[i];
-  a.g = sw->gravity;
-  a.roe = sw->roestab ? 1 : 0;
-  a.res = res;
-  a.blocks = blocks;
+  SwhStep s;
+  s.a.lambda = lambda;
+  s.a.side_types = side_types;
+  if (farfield) for (int i = 0; i < 3; ++i) s.a.farfield[i] = farfield[i];
+  s.a.g = sw->gravity;
+  s.a.roe = sw->roestab ? 1 : 0;
+  s.pp.physics = MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED;
+  const char *names[3] = {"source H", "source Hux", "source Huy"};
+  for (int k = 0; k < 3; ++k) s.pp.f[k] = functions_.evaluate(names[k]);
+  s.pp.p[0] = sw->gravity;
+  return s;
+}
+
+// HDG element of shallowwaterHybridized, side part (kernels/swhdg_element.hip): residual and derivative blocks of the
+// interior + trace unknowns
+void AssemblyManager::swhdgElementBlocks(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
+                                         const uint8_t *side_types, const double *farfield, double *res, double *blocks) {
+  MHA_REQUIRE(lambda && (res || blocks), MHA_ERR_INVALID, "null trace values or outputs");
+  for (const auto &vi : vars_) MHA_REQUIRE(vi.order == 1, MHA_ERR_INVALID, "the HDG element is built for order-1 variables");
+  SwhStep s = swhStepArgs(u, u_prev, u_stage, lambda, side_types, farfield, false);
+  s.a.res = res;
+  s.a.blocks = blocks;
   timedBegin();
-  launch_swhdg_element(blockDev(), sideTablesDev(), a, time_, stream_);
+  launch_swhdg_element(blockDev(), sideTablesDev(), s.a, time_, stream_);
   timedEnd();
 }
 
@@ -941,26 +956,11 @@ bool AssemblyManager::swhdgFusedUsable() const {
 
 void AssemblyManager::swhdgCondensedElement(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
                                             const uint8_t *side_types, const double *farfield, SwhFusedOut o) {
-  requireReady(false);
-  shallowwaterHybridized *sw = dynamic_cast<shallowwaterHybridized *>(physics_.get());
-  MHA_REQUIRE(sw != nullptr, MHA_ERR_INVALID, "the block's physics module is not shallowwaterHybridized");
   MHA_REQUIRE(lambda != nullptr, MHA_ERR_INVALID, "null trace values");
   for (const auto &vi : vars_) MHA_REQUIRE(vi.order == 1, MHA_ERR_INVALID, "the HDG element is built for order-1 variables");
-  bindState(u, u_prev, u_stage);
-  prepareSideTables();
-  SwhElementDev a;
-  a.lambda = lambda;
-  a.side_types = side_types;
-  if (farfield) for (int i = 0; i < 3; ++i) a.farfield[i] = farfield[i];
-  a.g = sw->gravity;
-  a.roe = sw->roestab ? 1 : 0;
-  PhysParamsDev pp;
-  pp.physics = MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED;
-  const char *names[3] = {"source H", "source Hux", "source Huy"};
-  for (int k = 0; k < 3; ++k) pp.f[k] = functions_.evaluate(names[k]);
-  pp.p[0] = sw->gravity;
+  const SwhStep s = swhStepArgs(u, u_prev, u_stage, lambda, side_types, farfield, false);
   timedBegin();
-  launch_swhdg_fused(blockDev(), sideTablesDev(), a, time_, pp, o, stream_);
+  launch_swhdg_fused(blockDev(), sideTablesDev(), s.a, time_, s.pp, o, stream_);
   timedEnd();
 }
 
@@ -983,54 +983,22 @@ void AssemblyManager::swhdgSetSubgrids(int m) {
 // The fused element step of a subgrid layout (kernels/swhdg_subgrid_fused.hip): outputs per macro element.
 void AssemblyManager::swhdgCondensedSubgrid(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
                                             const uint8_t *side_types, const double *farfield, SwhFusedOut o) {
-  requireReady(false);
-  shallowwaterHybridized *sw = dynamic_cast<shallowwaterHybridized *>(physics_.get());
-  MHA_REQUIRE(sw != nullptr, MHA_ERR_INVALID, "the block's physics module is not shallowwaterHybridized");
-  MHA_REQUIRE(subgrid_m_ > 0, MHA_ERR_STATE, "no subgrid layout: call mha_swhdg_set_subgrids first");
   MHA_REQUIRE(lambda != nullptr, MHA_ERR_INVALID, "null trace values");
-  bindState(u, u_prev, u_stage);
-  prepareSideTables();
-  SwhElementDev a;
-  a.lambda = lambda;
-  a.side_types = side_types;
-  if (farfield) for (int i = 0; i < 3; ++i) a.farfield[i] = farfield[i];
-  a.g = sw->gravity;
-  a.roe = sw->roestab ? 1 : 0;
-  PhysParamsDev pp;
-  pp.physics = MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED;
-  const char *names[3] = {"source H", "source Hux", "source Huy"};
-  for (int k = 0; k < 3; ++k) pp.f[k] = functions_.evaluate(names[k]);
-  pp.p[0] = sw->gravity;
+  const SwhStep s = swhStepArgs(u, u_prev, u_stage, lambda, side_types, farfield, true);
   timedBegin();
-  launch_swhdg_subgrid_fused(subgrid_m_, blockDev(), sideTablesDev(), a, time_, pp, o, stream_);
+  launch_swhdg_subgrid_fused(subgrid_m_, blockDev(), sideTablesDev(), s.a, time_, s.pp, o, stream_);
   timedEnd();
 }
 
 // The uncondensed blocks of a subgrid layout by the plain kernel (kernels/swhdg_subgrid_blocks.hip).
 void AssemblyManager::swhdgSubgridBlocks(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
                                          const uint8_t *side_types, const double *farfield, double *res, double *blocks) {
-  requireReady(false);
-  shallowwaterHybridized *sw = dynamic_cast<shallowwaterHybridized *>(physics_.get());
-  MHA_REQUIRE(sw != nullptr, MHA_ERR_INVALID, "the block's physics module is not shallowwaterHybridized");
-  MHA_REQUIRE(subgrid_m_ > 0, MHA_ERR_STATE, "no subgrid layout: call mha_swhdg_set_subgrids first");
   MHA_REQUIRE(lambda && (res || blocks), MHA_ERR_INVALID, "null trace values or outputs");
-  bindState(u, u_prev, u_stage);
-  prepareSideTables();
-  SwhElementDev a;
-  a.lambda = lambda;
-  a.side_types = side_types;
-  if (farfield) for (int i = 0; i < 3; ++i) a.farfield[i] = farfield[i];
-  a.g = sw->gravity;
-  a.roe = sw->roestab ? 1 : 0;
-  a.res = res;
-  a.blocks = blocks;
-  PhysParamsDev pp;
-  pp.physics = MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED;
-  const char *names[3] = {"source H", "source Hux", "source Huy"};
-  for (int k = 0; k < 3; ++k) pp.f[k] = functions_.evaluate(names[k]);
-  pp.p[0] = sw->gravity;
+  SwhStep s = swhStepArgs(u, u_prev, u_stage, lambda, side_types, farfield, true);
+  s.a.res = res;
+  s.a.blocks = blocks;
   timedBegin();
-  launch_swhdg_subgrid_blocks(subgrid_m_, blockDev(), sideTablesDev(), a, time_, pp, stream_);
+  launch_swhdg_subgrid_blocks(subgrid_m_, blockDev(), sideTablesDev(), s.a, time_, s.pp, stream_);
   timedEnd();
 }
 
@@ -1064,32 +1032,38 @@ void AssemblyManager::subgridSolve(double *u, const double *u_prev, const double
   MHA_REQUIRE(max_iter >= 1 && tol >= 0.0, MHA_ERR_INVALID, "bad iteration limits");
   MHA_REQUIRE(workspace_bytes >= subgridWorkspaceBytes(), MHA_ERR_INVALID,
               "workspace too small: " << workspace_bytes << " < " << subgridWorkspaceBytes());
-  if (subgrid_m_ > 0) {
-    // a subgrid layout is set: one workgroup per macro element and pass (kernels/swhdg_subgrid_fused.hip), the same protocol
-    // with norms and du over the n_int unknowns of a macro element; iters / resnorm / schur / gvec are per macro element
-    const size_t Em = static_cast<size_t>(nelem_) / (subgrid_m_ * subgrid_m_);
-    double *rn0 = static_cast<double *>(workspace);
-    MHA_HIP(hipMemsetAsync(num_singular, 0, sizeof(int32_t), stream_));
+  // The loop on a fused element step (swhdgCondensedSubgrid or swhdgCondensedElement): max_iter passes that keep the loop
+  // state in rn0 / active and advance u, then the closing pass at the final state for S and g.  The subgrid kernel's
+  // closing pass takes no flags; the one-element kernel's keeps them (it only reads them when it updates u).
+  auto fusedLoop = [&](auto step, double *rn0, int32_t *active, bool closing_keeps_active) {
     SwhFusedOut o;
     o.singular = num_singular;
     o.tol = tol;
     o.rn0 = rn0;
     o.scaled = resnorm_scaled;
     o.iters = iters;
-    o.active = reinterpret_cast<int32_t *>(rn0 + Em);
+    o.active = active;
     for (int pass = 0; pass < max_iter; ++pass) {
       o.pass = pass;
       o.update_u = u;
-      swhdgCondensedSubgrid(u, u_prev, u_stage, lambda, side_types, farfield, o);
+      (this->*step)(u, u_prev, u_stage, lambda, side_types, farfield, o);
     }
     if (schur || gvec) {
       o.pass = -1;
       o.update_u = nullptr;
-      o.active = nullptr;
+      if (!closing_keeps_active) o.active = nullptr;
       o.schur = schur;
       o.gvec = gvec;
-      swhdgCondensedSubgrid(u, u_prev, u_stage, lambda, side_types, farfield, o);
+      (this->*step)(u, u_prev, u_stage, lambda, side_types, farfield, o);
     }
+  };
+  if (subgrid_m_ > 0) {
+    // a subgrid layout is set: one workgroup per macro element and pass (kernels/swhdg_subgrid_fused.hip), the same protocol
+    // with norms and du over the n_int unknowns of a macro element; iters / resnorm / schur / gvec are per macro element
+    const size_t Em = static_cast<size_t>(nelem_) / (subgrid_m_ * subgrid_m_);
+    double *rn0 = static_cast<double *>(workspace);
+    MHA_HIP(hipMemsetAsync(num_singular, 0, sizeof(int32_t), stream_));
+    fusedLoop(&AssemblyManager::swhdgCondensedSubgrid, rn0, reinterpret_cast<int32_t *>(rn0 + Em), false);
     return;
   }
   if (!subgrid_checked_) {  // interior unknowns must be element-local (discontinuous): checked once per mesh
@@ -1109,25 +1083,7 @@ void AssemblyManager::subgridSolve(double *u, const double *u_prev, const double
   if (swhdgFusedUsable()) {
     // one kernel per pass: assembly, bookkeeping, element-local solve and sol += du fused (kernels/swhdg_fused.hip); the
     // [36 x 36] blocks never reach memory
-    SwhFusedOut o;
-    o.singular = num_singular;
-    o.tol = tol;
-    o.rn0 = rn0;
-    o.scaled = resnorm_scaled;
-    o.iters = iters;
-    o.active = active;
-    for (int pass = 0; pass < max_iter; ++pass) {
-      o.pass = pass;
-      o.update_u = u;
-      swhdgCondensedElement(u, u_prev, u_stage, lambda, side_types, farfield, o);
-    }
-    if (schur || gvec) {
-      o.pass = -1;
-      o.update_u = nullptr;
-      o.schur = schur;
-      o.gvec = gvec;
-      swhdgCondensedElement(u, u_prev, u_stage, lambda, side_types, farfield, o);
-    }
+    fusedLoop(&AssemblyManager::swhdgCondensedElement, rn0, active, true);
     return;
   }
   auto assemble = [&](int pass) {

@@ -126,6 +126,10 @@ class AssemblyManager {
   void launchRowOwner(bool compute_jacobian, bool overwrite, double *res, double *crs_vals, bool deterministic = false);
   BlockDev blockDev() const;
   void bindState(const double *u, const double *u_prev, const double *u_stage);
+  // shared setup of the four HDG element steps (swhdg*): checks, bound state, side tables, kernel arguments
+  struct SwhStep { SwhElementDev a; PhysParamsDev pp; };
+  SwhStep swhStepArgs(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
+                      const uint8_t *side_types, const double *farfield, bool need_layout);
   void timedBegin();
   void timedEnd();
 

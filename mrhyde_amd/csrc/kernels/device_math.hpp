@@ -7,6 +7,51 @@
 
 namespace mha {
 
+// Stage value and time derivative of solution row `row` as Workset::computeSolnTransientSeeded seeds them (seedwhat == 1,
+// reference: src/tools/workset.cpp:589-623), with cu = tm.u[row]:
+//   ue = alpha_u cu + beta_u,  beta_u = (1 - alpha_u) u_prev[0] + sum_{s < stage} stage_ratio[s] (u_stage[s] - u_prev[0])
+//   ud = alpha_t cu + beta_t,  beta_t = timewt * sum_{s = 1..nsteps} bdf[s] u_prev[s - 1]
+// The one statement of the time integrator's formula on the device: every kernel that reads the solution vector calls it.
+// GUARDED: the formula applies when tm.transient is set, steady runs get ue = cu, ud = 0; kernels compiled per transient /
+// steady pass false (their `if constexpr (TR)` is the guard).  WITH_DT = false leaves ud alone and never reads the BDF
+// history.
+template <bool WITH_DT, bool GUARDED>
+__device__ __forceinline__ void stage_seed(const TimeDev &tm, int row, double cu, double &ue, double &ud) {
+  if constexpr (GUARDED) {
+    ue = cu;
+    if constexpr (WITH_DT) ud = 0.0;
+  }
+  if (!GUARDED || tm.transient) {
+    const double *cp = tm.u_prev + (size_t)row * tm.nsteps;
+    const double *cs = tm.u_stage + (size_t)row * tm.nstages;
+    double beta_u = (1.0 - tm.alpha_u) * cp[0];
+    for (int s = 0; s < tm.stage; ++s) beta_u += tm.stage_ratio[s] * (cs[s] - cp[0]);
+    double beta_t = 0.0;
+    if constexpr (WITH_DT) {
+      for (int s = 1; s < tm.nsteps + 1; ++s) beta_t += tm.bdf[s] * cp[s - 1];
+      beta_t *= tm.timewt;
+    }
+    ue = tm.alpha_u * cu + beta_u;
+    if constexpr (WITH_DT) ud = tm.alpha_t * cu + beta_t;
+  }
+}
+
+// value and time derivative.  The first form is for callers that have loaded cu already.
+__device__ __forceinline__ void stage_state(const TimeDev &tm, int row, double cu, double &ue, double &ud) {
+  stage_seed<true, true>(tm, row, cu, ue, ud);
+}
+__device__ __forceinline__ void stage_state(const TimeDev &tm, int row, double &ue, double &ud) {
+  stage_seed<true, true>(tm, row, tm.u[row], ue, ud);
+}
+
+// value only (boundary terms and the modules without a time derivative)
+__device__ __forceinline__ double stage_value(const TimeDev &tm, int row, double cu) {
+  double ue, ud;
+  stage_seed<false, true>(tm, row, cu, ue, ud);
+  return ue;
+}
+__device__ __forceinline__ double stage_value(const TimeDev &tm, int row) { return stage_value(tm, row, tm.u[row]); }
+
 // Inverse and determinant of the cell Jacobian (CellTools::setJacobianInv/Det,
 // reference: src/interfaces/discretizationInterface.cpp:923-929).
 template <int DIM>

@@ -261,17 +261,8 @@ __global__ __launch_bounds__(kEngineThreads) void point_engine_kernel(BlockDev b
       if (REGB && q_stream && have_pf) { pos = pos_k; row = row_pf; cu = cu_pf; }
       else { pos = b.offsets[f]; row = b.lids[(size_t)e * n + pos]; cu = tm.u[row]; }
       const double sg = vl.orient ? (double)vl.orient[(size_t)e * n + f] : 1.0;
-      double ue = cu, ud = 0.0;
-      if (tm.transient) {  // Workset::computeSolnTransientSeeded (workset.cpp:589-623)
-        const double *cp = tm.u_prev + (size_t)row * tm.nsteps, *cs = tm.u_stage + (size_t)row * tm.nstages;
-        double beta_u = (1.0 - tm.alpha_u) * cp[0];
-        for (int st = 0; st < tm.stage; ++st) beta_u += tm.stage_ratio[st] * (cs[st] - cp[0]);
-        double beta_t = 0.0;
-        for (int st = 1; st < tm.nsteps + 1; ++st) beta_t += tm.bdf[st] * cp[st - 1];
-        beta_t *= tm.timewt;
-        ue = tm.alpha_u * cu + beta_u;
-        ud = tm.alpha_t * cu + beta_t;
-      }
+      double ue, ud;
+      stage_state(tm, row, cu, ue, ud);
       s_u[f] = ue * sg;
       s_ud[f] = ud * sg;
       s_sgn[f] = sg;

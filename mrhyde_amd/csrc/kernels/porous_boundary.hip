@@ -70,15 +70,7 @@ __global__ __launch_bounds__(256) void porous_flux_kernel(BlockDev b, SideTables
       for (int d = 0; d < DIM; ++d) vdotn += J[d * DIM + c] * nrm[d];
       vdotn *= sg * phi / det;
       const int row = b.lids[(size_t)e * n + b.offsets[u0 + dof]];
-      const double cu = tm.u[row];
-      double ue = cu;
-      if (tm.transient) {  // Workset::computeSolnTransientSeeded (workset.cpp:589-623)
-        const double *cp = tm.u_prev + (size_t)row * tm.nsteps, *cs = tm.u_stage + (size_t)row * tm.nstages;
-        double beta_u = (1.0 - tm.alpha_u) * cp[0];
-        for (int st_ = 0; st_ < tm.stage; ++st_) beta_u += tm.stage_ratio[st_] * (cs[st_] - cp[0]);
-        ue = tm.alpha_u * cu + beta_u;
-      }
-      f += ue * vdotn;
+      f += stage_value(tm, row) * vdotn;
       if (bd.dflux_du) bd.dflux_du[(size_t)idx * n + u0 + dof] = tm.alpha_u * vdotn;
     }
     bd.flux[idx] = f;

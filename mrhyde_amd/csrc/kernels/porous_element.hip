@@ -60,15 +60,7 @@ __device__ __forceinline__ void porous_element_body(const BlockDev &b, const Var
     pos[f] = b.offsets[f];
     const int row = L[pos[f]];
     sg[f] = (vl.orient && f > 0) ? (double)vl.orient[(size_t)e * N + f] : 1.0;
-    const double cu = tm.u[row];
-    double ue = cu;
-    if (tm.transient) {  // Workset::computeSolnTransientSeeded (workset.cpp:589-623); the module has no time derivative
-      const double *cp = tm.u_prev + (size_t)row * tm.nsteps, *cs = tm.u_stage + (size_t)row * tm.nstages;
-      double beta_u = (1.0 - tm.alpha_u) * cp[0];
-      for (int s = 0; s < tm.stage; ++s) beta_u += tm.stage_ratio[s] * (cs[s] - cp[0]);
-      ue = tm.alpha_u * cu + beta_u;
-    }
-    u[f] = ue;
+    u[f] = stage_value(tm, row);  // the module has no time derivative
   }
   double xn[DOF ? 1 : NN][DIM];
   double *sx = sm + (size_t)tid * NN * DIM;  // DOF: the thread's own vertices (read back by the same thread: no barrier)
@@ -441,15 +433,7 @@ __global__ __launch_bounds__(256) void porous_uniform_residual_kernel(BlockDev b
 #pragma unroll
   for (int f = 0; f < N; ++f) {
     row[f] = L[b.offsets[f]];
-    const double cu = tm.u[row[f]];
-    double ue = cu;
-    if (tm.transient) {  // Workset::computeSolnTransientSeeded (workset.cpp:589-623), as in the kernel above
-      const double *cp = tm.u_prev + (size_t)row[f] * tm.nsteps, *cs = tm.u_stage + (size_t)row[f] * tm.nstages;
-      double beta_u = (1.0 - tm.alpha_u) * cp[0];
-      for (int s = 0; s < tm.stage; ++s) beta_u += tm.stage_ratio[s] * (cs[s] - cp[0]);
-      ue = tm.alpha_u * cu + beta_u;
-    }
-    u[f] = ue;
+    u[f] = stage_value(tm, row[f]);
   }
   // source integral: x_q = first vertex + the common offset of point q
   const double *x0 = b.nodes + (size_t)e * NN * DIM;

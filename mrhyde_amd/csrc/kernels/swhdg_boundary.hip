@@ -34,15 +34,7 @@ __global__ __launch_bounds__(64 * kSwWaves) void swhdg_boundary_kernel(BlockDev 
   // gather + seeding values (lane = flattened (variable, dof))
   if (active && lane < nt) {
     const int row = L[b.offsets[lane]];
-    const double cu = tm.u[row];
-    double ue = cu;
-    if (tm.transient) {
-      const double *cp = tm.u_prev + (size_t)row * tm.nsteps, *cs = tm.u_stage + (size_t)row * tm.nstages;
-      double beta_u = (1.0 - tm.alpha_u) * cp[0];
-      for (int st_ = 0; st_ < tm.stage; ++st_) beta_u += tm.stage_ratio[st_] * (cs[st_] - cp[0]);
-      ue = tm.alpha_u * cu + beta_u;
-    }
-    s_u[wv][lane] = ue;
+    s_u[wv][lane] = stage_value(tm, row);
     s_row[wv][lane] = row;
   }
   __syncthreads();

@@ -39,15 +39,7 @@ __global__ __launch_bounds__(64 * kHdgWaves) void swhdg_element_kernel(BlockDev 
   const int32_t *L = b.lids + (size_t)e * 12;
   if (active && lane < 12) {
     const int row = L[b.offsets[lane]];
-    const double cu = tm.u[row];
-    double ue = cu;
-    if (tm.transient) {
-      const double *cp = tm.u_prev + (size_t)row * tm.nsteps, *cs = tm.u_stage + (size_t)row * tm.nstages;
-      double beta_u = (1.0 - tm.alpha_u) * cp[0];
-      for (int s = 0; s < tm.stage; ++s) beta_u += tm.stage_ratio[s] * (cs[s] - cp[0]);
-      ue = tm.alpha_u * cu + beta_u;
-    }
-    s_u[wv][lane] = ue;
+    s_u[wv][lane] = stage_value(tm, row);
   }
   if (active && lane >= 32 && lane < 56) s_l[wv][lane - 32] = a.lambda[(size_t)e * 24 + lane - 32];
   __syncthreads();

@@ -51,18 +51,8 @@ __global__ __launch_bounds__(64 * kFuWaves, 3) void swhdg_fused_kernel(BlockDev 
   if (active && lane < 12) {
     const int row = L[b.offsets[lane]];
     myrow = row;
-    const double cu = tm.u[row];
-    double ue = cu, ud = 0.0;
-    if (tm.transient) {  // Workset::computeSolnTransientSeeded (workset.cpp:589-623)
-      const double *cp = tm.u_prev + (size_t)row * tm.nsteps, *cs = tm.u_stage + (size_t)row * tm.nstages;
-      double beta_u = (1.0 - tm.alpha_u) * cp[0];
-      for (int s = 0; s < tm.stage; ++s) beta_u += tm.stage_ratio[s] * (cs[s] - cp[0]);
-      double beta_t = 0.0;
-      for (int s = 1; s < tm.nsteps + 1; ++s) beta_t += tm.bdf[s] * cp[s - 1];
-      beta_t *= tm.timewt;
-      ue = tm.alpha_u * cu + beta_u;
-      ud = tm.alpha_t * cu + beta_t;
-    }
+    double ue, ud;
+    stage_state(tm, row, ue, ud);
     s_u[wv][lane] = ue;
     s_ud[wv][lane] = ud;
   }
@@ -268,18 +258,7 @@ __global__ __launch_bounds__(64 * kFuWaves, 3) void swhdg_fused_kernel(BlockDev 
     double nrm = 0.0;
 #pragma unroll
     for (int r = 0; r < 12; ++r) nrm = fmax(nrm, fabs(col[r]));
-    const int64_t eo = e - b.e_begin;
-    if (o.pass == 0) {
-      o.rn0[eo] = nrm;
-      o.scaled[eo] = nrm > 0.0 ? 1.0 : 0.0;
-      o.iters[eo] = 1;
-      o.active[eo] = (nrm > 0.0 ? 1.0 : 0.0) > o.tol ? 1 : 0;
-    } else if (o.active[eo]) {
-      const double sc = nrm / o.rn0[eo];
-      o.scaled[eo] = sc;
-      o.iters[eo] += 1;
-      o.active[eo] = sc > o.tol ? 1 : 0;
-    }
+    swh_loop_bookkeeping(o, e - b.e_begin, nrm);
   }
   // ---- static condensation in registers ----
   const int64_t eo = e - b.e_begin;

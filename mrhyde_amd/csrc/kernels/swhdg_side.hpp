@@ -4,6 +4,7 @@
 // computeStabilizationTerm :487-588, computeBoundaryTerm :595-758, computeFlux :270-368.  State order H, Hux, Huy
 // (2-D); S = interior state, Sh = trace state ("aux" variables), Sinf = far-field state.
 #pragma once
+#include "device_types.hpp"
 #include "dual.hpp"
 
 namespace mha {
@@ -162,6 +163,31 @@ __device__ __forceinline__ void swh_interface_flux(int side_type, bool roe, cons
   swh_stab_term(S, Sh, nx, ny, g, roe, st);
 #pragma unroll
   for (int i = 0; i < 3; ++i) out[i] = F[i][0] * nx + F[i][1] * ny + st[i];
+}
+
+// ---- shared by the two fused element steps (swhdg_fused.hip, swhdg_subgrid_fused.hip) ----
+
+// Loop bookkeeping of nonlinearSolver (subgridDtN_solver.cpp:909-1041; subgrid.hip: combine) for loop `idx` -- an element
+// or a macro element -- on the max norm of its interior residual at pass o.pass >= 0.  Returns whether the loop goes on.
+__device__ __forceinline__ int swh_loop_bookkeeping(const SwhFusedOut &o, int64_t idx, double nrm) {
+  int act;
+  if (o.pass == 0) {
+    o.rn0[idx] = nrm;
+    o.scaled[idx] = nrm > 0.0 ? 1.0 : 0.0;
+    o.iters[idx] = 1;
+    act = (nrm > 0.0 ? 1.0 : 0.0) > o.tol ? 1 : 0;
+    o.active[idx] = act;
+  } else {
+    act = o.active[idx];
+    if (act) {
+      const double sc = nrm / o.rn0[idx];
+      o.scaled[idx] = sc;
+      o.iters[idx] += 1;
+      act = sc > o.tol ? 1 : 0;
+      o.active[idx] = act;
+    }
+  }
+  return act;
 }
 
 }  // namespace mha

@@ -44,21 +44,4 @@ __device__ __forceinline__ int sg_row(const BlockDev &b, int m, int e0, int i, i
   return b.lids[(size_t)(e0 + ey * m + ex) * 12 + b.offsets[i * 4 + (ax - ex) + 2 * (ay - ey)]];
 }
 
-// stage value and time derivative of row `row` (Workset::computeSolnTransientSeeded, workset.cpp:589-623)
-__device__ __forceinline__ void sg_state(const TimeDev &tm, int row, double &ue, double &ud) {
-  const double cu = tm.u[row];
-  ue = cu;
-  ud = 0.0;
-  if (tm.transient) {
-    const double *cp = tm.u_prev + (size_t)row * tm.nsteps, *cs = tm.u_stage + (size_t)row * tm.nstages;
-    double beta_u = (1.0 - tm.alpha_u) * cp[0];
-    for (int s = 0; s < tm.stage; ++s) beta_u += tm.stage_ratio[s] * (cs[s] - cp[0]);
-    double beta_t = 0.0;
-    for (int s = 1; s < tm.nsteps + 1; ++s) beta_t += tm.bdf[s] * cp[s - 1];
-    beta_t *= tm.timewt;
-    ue = tm.alpha_u * cu + beta_u;
-    ud = tm.alpha_t * cu + beta_t;
-  }
-}
-
 }  // namespace mha

@@ -48,10 +48,7 @@ __global__ __launch_bounds__(kSbThreads) void swhdg_subgrid_blocks_kernel(int M,
       const double *xn = b.nodes + (size_t)(e0 + ey * M + ex) * NN * DIM;
       double ul[3][4];
       for (int i = 0; i < 3; ++i)
-        for (int dof = 0; dof < 4; ++dof) {
-          double ud;
-          sg_state(tm, sg_row(b, M, e0, i, sg_node(M, ex, ey, dof)), ul[i][dof], ud);
-        }
+        for (int dof = 0; dof < 4; ++dof) ul[i][dof] = stage_value(tm, sg_row(b, M, e0, i, sg_node(M, ex, ey, dof)));
       for (int q = 0; q < nqs; ++q) {
         double Ji[DIM * DIM], nrm[DIM], w, x[DIM];
         side_point<DIM>(xn, st, s, q, Ji, nrm, w, x);
@@ -93,7 +90,7 @@ __global__ __launch_bounds__(kSbThreads) void swhdg_subgrid_blocks_kernel(int M,
         const double *xn = b.nodes + (size_t)(e0 + se) * NN * DIM;
         double ul[3][4], udl[3][4];
         for (int i = 0; i < 3; ++i)
-          for (int dof = 0; dof < 4; ++dof) sg_state(tm, sg_row(b, M, e0, i, sg_node(M, ex, ey, dof)), ul[i][dof], udl[i][dof]);
+          for (int dof = 0; dof < 4; ++dof) stage_state(tm, sg_row(b, M, e0, i, sg_node(M, ex, ey, dof)), ul[i][dof], udl[i][dof]);
         for (int q = 0; q < nq; ++q) {
           double J[DIM * DIM] = {0, 0, 0, 0}, Ji[DIM * DIM], det, x[DIM] = {0, 0}, xi[DIM] = {0, 0};
           const double vx[4] = {-1.0, 1.0, 1.0, -1.0}, vy[4] = {-1.0, -1.0, 1.0, 1.0};

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(kSgThreads) void swhdg_subgrid_fused_kernel(BlockDe
   for (int r = tid; r < NI; r += kSgThreads) {
     const int row = sg_row(b, M, e0, r / NP, r % NP);
     double ue, ud;
-    sg_state(tm, row, ue, ud);
+    stage_state(tm, row, ue, ud);
     s_rows[r] = row;
     s_u[r] = ue;
     s_ud[r] = ud;
@@ -246,26 +246,7 @@ __global__ __launch_bounds__(kSgThreads) void swhdg_subgrid_fused_kernel(BlockDe
       for (int i = lane; i < NI; i += 64) nrm = fmax(nrm, fabs(A[i * LD + N]));
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) nrm = fmax(nrm, __shfl_xor(nrm, off));
-      if (lane == 0) {
-        int act;
-        if (o.pass == 0) {
-          o.rn0[me] = nrm;
-          o.scaled[me] = nrm > 0.0 ? 1.0 : 0.0;
-          o.iters[me] = 1;
-          act = (nrm > 0.0 ? 1.0 : 0.0) > o.tol ? 1 : 0;
-          o.active[me] = act;
-        } else {
-          act = o.active[me];
-          if (act) {
-            const double sc = nrm / o.rn0[me];
-            o.scaled[me] = sc;
-            o.iters[me] += 1;
-            act = sc > o.tol ? 1 : 0;
-            o.active[me] = act;
-          }
-        }
-        s_go[0] = act;
-      }
+      if (lane == 0) s_go[0] = swh_loop_bookkeeping(o, me, nrm);
     }
   } else if (tid == 0 && o.active) {
     s_go[0] = o.active[me];

@@ -110,15 +110,7 @@ __global__ __launch_bounds__(kK1tThreads, 2) void thermal_affine_residual_kernel
     const double cu = tm.u[row];
     double ue = cu;
     if constexpr (TR) {
-      const double *cp = tm.u_prev + (size_t)row * tm.nsteps;
-      const double *cs = tm.u_stage + (size_t)row * tm.nstages;
-      double beta_u = (1.0 - tm.alpha_u) * cp[0];
-      for (int s = 0; s < tm.stage; ++s) beta_u += tm.stage_ratio[s] * (cs[s] - cp[0]);
-      double beta_t = 0.0;
-      for (int s = 1; s < tm.nsteps + 1; ++s) beta_t += tm.bdf[s] * cp[s - 1];
-      beta_t *= tm.timewt;
-      ue = tm.alpha_u * cu + beta_u;
-      Ud[ib] = tm.alpha_t * cu + beta_t;
+      stage_seed<true, false>(tm, row, cu, ue, Ud[ib]);
     }
     U[ib] = ue;
   }
@@ -292,7 +284,7 @@ __global__ __launch_bounds__(kK1wThreads, (TR || EXPR || !SEPK) ? 2 : 3) void th
 #pragma unroll
     for (int ib = 0; ib < N; ++ib) kpos[ib] = loc[ib * kK1wThreads];
   }
-  // ---- A. performGather + computeSoln*Seeded values (workset.cpp:589-623), once per listed row ----
+  // ---- A. performGather + computeSoln*Seeded values (stage_seed), once per listed row ----
   // (four rows per thread and pass, every load of a stage issued before the first use: the loop would otherwise run its
   //  dependent loads -- row id, then value -- one row at a time)
   constexpr int KB = 4;
@@ -314,15 +306,7 @@ __global__ __launch_bounds__(kK1wThreads, (TR || EXPR || !SEPK) ? 2 : 3) void th
       s_row[i] = fx[k] ? ~row[k] : row[k];
       double ue = cu[k];
       if constexpr (TR) {
-        const double *cp = tm.u_prev + (size_t)row[k] * tm.nsteps;
-        const double *cs = tm.u_stage + (size_t)row[k] * tm.nstages;
-        double beta_u = (1.0 - tm.alpha_u) * cp[0];
-        for (int s = 0; s < tm.stage; ++s) beta_u += tm.stage_ratio[s] * (cs[s] - cp[0]);
-        double beta_t = 0.0;
-        for (int s = 1; s < tm.nsteps + 1; ++s) beta_t += tm.bdf[s] * cp[s - 1];
-        beta_t *= tm.timewt;
-        ue = tm.alpha_u * cu[k] + beta_u;
-        s_tab[pl.max_rows + i] = tm.alpha_t * cu[k] + beta_t;
+        stage_seed<true, false>(tm, row[k], cu[k], ue, s_tab[pl.max_rows + i]);
       }
       s_tab[i] = ue;
     }

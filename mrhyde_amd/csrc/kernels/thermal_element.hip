@@ -71,19 +71,8 @@ __global__ __launch_bounds__(64 * EPB) void thermal_element_kernel(BlockDev b, T
     for (int i = lane; i < NN * DIM; i += 64) wv[S::O_XN + i] = b.nodes[(size_t)e * NN * DIM + i];
     for (int dof = lane; dof < N; dof += 64) {
       const int row = b.lids[(size_t)e * N + b.offsets[dof]];
-      const double cu = tm.u[row];
-      double ue = cu, ud = 0.0;
-      if (tm.transient) {
-        const double *cp = tm.u_prev + (size_t)row * tm.nsteps;
-        const double *cs = tm.u_stage + (size_t)row * tm.nstages;
-        double beta_u = (1.0 - tm.alpha_u) * cp[0];
-        for (int s = 0; s < tm.stage; ++s) beta_u += tm.stage_ratio[s] * (cs[s] - cp[0]);
-        double beta_t = 0.0;
-        for (int s = 1; s < tm.nsteps + 1; ++s) beta_t += tm.bdf[s] * cp[s - 1];
-        beta_t *= tm.timewt;
-        ue = tm.alpha_u * cu + beta_u;
-        ud = tm.alpha_t * cu + beta_t;
-      }
+      double ue, ud;
+      stage_state(tm, row, ue, ud);
       wv[S::O_UE + dof] = ue;
       wv[S::O_UD + dof] = ud;
     }

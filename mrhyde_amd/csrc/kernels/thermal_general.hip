@@ -127,15 +127,7 @@ __global__ __launch_bounds__((GK<DIM, P, NQ1, TR>::NT), kTgMinWaves) void therma
       const double cu = tm.u[row];
       double ue = cu;
       if constexpr (TR) {
-        const double *cp = tm.u_prev + (size_t)row * tm.nsteps;
-        const double *cs = tm.u_stage + (size_t)row * tm.nstages;
-        double beta_u = (1.0 - tm.alpha_u) * cp[0];
-        for (int s = 0; s < tm.stage; ++s) beta_u += tm.stage_ratio[s] * (cs[s] - cp[0]);
-        double beta_t = 0.0;
-        for (int s = 1; s < tm.nsteps + 1; ++s) beta_t += tm.bdf[s] * cp[s - 1];
-        beta_t *= tm.timewt;
-        ue = tm.alpha_u * cu + beta_u;
-        E[S::O_UD + dof] = tm.alpha_t * cu + beta_t;
+        stage_seed<true, false>(tm, row, cu, ue, E[S::O_UD + dof]);
       }
       E[S::O_UE + dof] = ue;
     }

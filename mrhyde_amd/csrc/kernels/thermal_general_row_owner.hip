@@ -226,16 +226,7 @@ __global__ __launch_bounds__(512) void thermal_general_row_owner_kernel(BlockDev
       const double cu = tm.u[row];                                                                                  \
       ue[k] = cu;                                                                                                   \
       ud[k] = 0.0;                                                                                                  \
-      if constexpr (TR) { /* Workset::computeSolnTransientSeeded, value parts (workset.cpp:589-623) */              \
-        const double *cp = tm.u_prev + (size_t)row * tm.nsteps, *cs = tm.u_stage + (size_t)row * tm.nstages;        \
-        double beta_u = (1.0 - tm.alpha_u) * cp[0];                                                                 \
-        for (int s = 0; s < tm.stage; ++s) beta_u += tm.stage_ratio[s] * (cs[s] - cp[0]);                           \
-        double beta_t = 0.0;                                                                                        \
-        for (int s = 1; s < tm.nsteps + 1; ++s) beta_t += tm.bdf[s] * cp[s - 1];                                    \
-        beta_t *= tm.timewt;                                                                                        \
-        ue[k] = tm.alpha_u * cu + beta_u;                                                                           \
-        ud[k] = tm.alpha_t * cu + beta_t;                                                                           \
-      }                                                                                                             \
+      if constexpr (TR) stage_seed<true, false>(tm, row, cu, ue[k], ud[k]);                                                \
     }                                                                                                               \
     _Pragma("unroll") for (int k = 0; k < XI; ++k) {                                                                \
       const int i = min(tid + k * PT, T_ * NN * DIM - 1), t = i / (NN * DIM);                                       \

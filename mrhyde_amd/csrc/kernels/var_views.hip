@@ -83,18 +83,8 @@ __global__ __launch_bounds__(256) void var_fields_kernel(BlockDev b, TimeDev tm,
     double val[3] = {0, 0, 0}, dot[3] = {0, 0, 0}, g[3] = {0, 0, 0}, dv = 0.0;
     for (int f = 0; f < card; ++f) {
       const int row = L[b.offsets[var_off + f]];
-      const double cu = tm.u[row];
-      double ue = cu, ud = 0.0;
-      if (tm.transient) {  // Workset::computeSolnTransientSeeded, value part (workset.cpp:589-623)
-        const double *cp = tm.u_prev + (size_t)row * tm.nsteps, *cs = tm.u_stage + (size_t)row * tm.nstages;
-        double beta_u = (1.0 - tm.alpha_u) * cp[0];
-        for (int st = 0; st < tm.stage; ++st) beta_u += tm.stage_ratio[st] * (cs[st] - cp[0]);
-        double beta_t = 0.0;
-        for (int st = 1; st < tm.nsteps + 1; ++st) beta_t += tm.bdf[st] * cp[st - 1];
-        beta_t *= tm.timewt;
-        ue = tm.alpha_u * cu + beta_u;
-        ud = tm.alpha_t * cu + beta_t;
-      }
+      double ue, ud;
+      stage_state(tm, row, ue, ud);
       const size_t o = ((size_t)k * card + f) * np + q;
       for (int c = 0; c < ncomp; ++c) {
         const double bv = basis[o * ncomp + c];

@@ -151,6 +151,52 @@ def test_boundary_residual_matches_oracle(oracle, order, qdeg, ncell, bc, roe):
     assert np.abs(vals.cpu().numpy() - vals_ref).max() < RTOL * np.abs(vals_ref).max()
 
 
+def test_boundary_residual_transient_stage_matches_oracle(oracle):
+    """The same on 2 x 2 order-1 elements at stage 1 of a two-stage tableau with a BDF-2 history: the interior state at the
+    side points is the seeded stage value, d res / d u carries alpha_u."""
+    torch = _torch()
+    import mrhyde_amd
+    from test_multi_gpu import make_block, transient_state, warp
+    from test_oracle_swhdg import all_element_sides
+    rng = np.random.default_rng(67)
+    H = oracle.HGRAD
+    ncell, qdeg, bc, roe = (2, 2), 2, 10, 1
+    m = warp(oracle.mesh_multi(2, ncell, [H, H, H], [1] * 3))
+    hrows = m["dof_var"] == 0
+    u = rng.uniform(-1, 1, m["ndof"])
+    u[hrows] = rng.uniform(1.0, 2.0, hrows.sum())
+    tr = transient_state(rng, m["ndof"], u)
+    for k in ("u_prev", "u_stage"):  # keep H of the seeded stage value positive
+        tr[k][hrows] = rng.uniform(1.0, 2.0, (hrows.sum(), 2))
+    rowptr, colind = oracle.build_graph(m["ndof"], m["lids"])
+    be, bs = all_element_sides(ncell)
+    shp = (len(be), oracle.side_sizes(2, qdeg)[1])
+    aux = np.dstack([rng.uniform(1.0, 2.0, shp), rng.uniform(-1, 1, shp), rng.uniform(-1, 1, shp)])
+    ff = np.dstack([rng.uniform(1.0, 2.0, shp), rng.uniform(-1, 1, shp), rng.uniform(-1, 1, shp)])
+    vals_ref, res_ref = np.zeros(rowptr[-1]), np.zeros(m["ndof"])
+    oracle.assemble_block_boundary(m, oracle.PHYS_SHALLOWWATER_HYBRIDIZED, qdeg, u, be, bs, bc, 0.0, rowptr=rowptr,
+                                   colind=colind, crs_vals=vals_ref, res=res_ref, params=[9.81, roe], aux=aux, farfield=ff,
+                                   transient=tr)
+    blk = make_block(m, "shallowwaterHybridized", qdeg, graph=(rowptr, colind))
+    blk.set_physics_parameter("Roe-like stabilization", roe)
+    blk.add_boundary_group("skeleton", bc, be, bs)
+    keep = []
+    for i, v in enumerate(("H", "Hux", "Huy")):
+        t = torch.tensor(np.ascontiguousarray(aux[..., i]), device="cuda")
+        f = torch.tensor(np.ascontiguousarray(ff[..., i]), device="cuda")
+        keep += [t, f]
+        blk.set_function("aux %s skeleton" % v, t)
+        blk.set_function("Far-field %s skeleton" % v, f)
+    blk.set_time_integration(True, 2, 2, 1, tr["dt"], tr["butcher_A"], tr["butcher_b"], tr["bdf"])
+    res = torch.zeros(m["ndof"], dtype=torch.float64, device="cuda")
+    vals = torch.zeros(len(colind), dtype=torch.float64, device="cuda")
+    blk.assemble_boundary(torch.tensor(u, device="cuda"), res, vals, u_prev=torch.tensor(tr["u_prev"], device="cuda"),
+                          u_stage=torch.tensor(tr["u_stage"], device="cuda"))
+    torch.cuda.synchronize()
+    assert np.abs(res.cpu().numpy() - res_ref).max() < RTOL * np.abs(res_ref).max()
+    assert np.abs(vals.cpu().numpy() - vals_ref).max() < RTOL * np.abs(vals_ref).max()
+
+
 def test_hdg_element_residual_vanishes_for_constant_state(oracle):
     """volumeResidual + boundaryResidual on all element sides with trace = constant interior state: zero residual
     (divergence theorem), on the device."""

@@ -173,6 +173,43 @@ def test_transient_seeding_matches_oracle(oracle, dim, order, qdeg, ncell, stage
     assert rel_err(res.cpu().numpy(), ref["res"]) < RTOL
 
 
+@pytest.mark.parametrize("dim,ncell", [(2, (2, 2)), (3, (2, 2, 2))])
+@pytest.mark.parametrize("path", ["element_atomic", "local_then_scatter"])
+def test_element_paths_transient_stage_matches_oracle(oracle, dim, ncell, path):
+    """The element kernels behind ELEMENT_ATOMIC (general-element kernel) and LOCAL_THEN_SCATTER (baseline element
+    kernel) at stage 1 of a two-stage tableau with a BDF-2 history: both sums of the stage formula carry weights."""
+    torch = _torch()
+    import mrhyde_amd
+    order, qdeg = 1, 2
+    m = perturbed(oracle, dim, order, ncell, seed=3)
+    rng = np.random.default_rng(17)
+    nd = m["ndof"]
+    u = rng.uniform(-1, 1, nd)
+    nsteps, nstages, stage = 2, 2, 1
+    A = np.array([[0.2928932188, 0.0], [0.7071067812, 0.2928932188]])
+    b = np.array([0.7071067812, 0.2928932188])
+    bdf = np.array([1.5, -2.0, 0.5])
+    tr = dict(u_prev=rng.uniform(-1, 1, (nd, nsteps)), u_stage=rng.uniform(-1, 1, (nd, nstages)), stage=stage,
+              butcher_A=A, butcher_b=b, bdf=bdf, dt=0.02)
+    ref = oracle.assemble_thermal(dim, order, qdeg, m["nodes"], m["lids"], m["offsets"], u, transient=tr, rho=1.3,
+                                  cp=0.7, diff=0.9, source=("const", 0.4))
+    blk = make_block(m, dim, order, qdeg, graph=(ref["rowptr"], ref["colind"]))
+    blk.set_function("thermal source", 0.4)
+    blk.set_function("thermal diffusion", 0.9)
+    blk.set_function("density", 1.3)
+    blk.set_function("specific heat", 0.7)
+    blk.set_time_integration(True, nsteps, nstages, stage, 0.02, A, b, bdf)
+    t = lambda a: torch.tensor(a, device="cuda")
+    res = torch.zeros(nd, dtype=torch.float64, device="cuda")
+    vals = torch.zeros(len(ref["colind"]), dtype=torch.float64, device="cuda")
+    p = {"element_atomic": mrhyde_amd.PATH_ELEMENT_ATOMIC, "local_then_scatter": mrhyde_amd.PATH_LOCAL_THEN_SCATTER}[path]
+    blk.assemble_jacres(t(u), res, vals, u_prev=t(tr["u_prev"]), u_stage=t(tr["u_stage"]), path=p)
+    torch.cuda.synchronize()
+    assert blk.info("last_path") == p
+    assert crs_err(vals.cpu().numpy(), ref) < RTOL
+    assert rel_err(res.cpu().numpy(), ref["res"]) < RTOL
+
+
 @pytest.mark.parametrize("dim,order,qdeg,ncell", [(2, 1, 2, (5, 4)), (3, 2, 4, (2, 2, 3)), (3, 1, 2, (3, 2, 2))])
 def test_workset_views_match_oracle(oracle, dim, order, qdeg, ncell):
     """basis / basis_grad / wts / x,y,z views of every workset (ragged last workset included)."""
