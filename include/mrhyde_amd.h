@@ -65,7 +65,8 @@ typedef struct mha_block_desc {
   int num_vars;                  /* thermal: 1 ("e"); porousMixed: 2 ("p","u");
                                     navierstokes: dim+1 ("ux","pr","uy"[,"uz"]);
                                     navierstokes + thermal: dim+2
-                                    ("ux","pr","uy"[,"uz"],"e")                  */
+                                    ("ux","pr","uy"[,"uz"],"e");
+                                    linearelasticity: dim ("dx","dy"[,"dz"])     */
   int basis_type[MHA_MAX_VARS];  /* MHA_BASIS_*, in the module's myvars order    */
   int basis_order[MHA_MAX_VARS]; /* Discretization: order                       */
   int quadrature_degree;         /* Discretization: quadrature (0 => 2*max order,
@@ -124,6 +125,20 @@ int mha_get_graph(mha_context *ctx, int32_t *rowptr_host, int32_t *colind_host);
  * Dirichlet rows and the generic "Flux" condition work per variable as on every block.  Deck strings in the
  * coordinates are accepted; deck strings that read the solution fields are refused.                              */
 #define MHA_PHYSICS_NAVIERSTOKES_THERMAL 5
+/* linearelasticity (src/physics/linearelasticity.cpp): displacements dx, dy[, dz], all HGRAD, in that order (:28-39;
+ * num_vars = dim, 2-D and 3-D).  Volume terms (:92-240 with computeStress :913-1099): row d gets
+ * sum_j sigma_dj d_j v - "source d<x|y|z>" v with sigma = lambda tr(grad u) I + mu (grad u + grad u^T); the parameter
+ * "incplanestress" (2-D) replaces the normal stresses by 4 mu d_x dx + 2 mu d_y dy and its mirror (:990-1000).  No
+ * time-derivative term.  Functions "lambda" (1), "mu" (0.5), "source dx|dy|dz" (0) (:72-76): constants, arrays,
+ * closed forms or deck strings in the coordinates.  Boundary groups (:244-672) act on ALL components of the side:
+ * MHA_BC_NEUMANN adds -g_d v with g_d = "Neumann d<x|y|z> <sidename>" (default 0; :361-371); MHA_BC_WEAK_DIRICHLET adds
+ * -(sigma n)_d v + penalty (u_d - D_d) v - form_param (b_d . grad v) with D_d = "Dirichlet d<x|y|z> <sidename>",
+ * penalty = "penalty" (10) * (lambda + 2 mu) / h, h = (sum of the side weights)^(1/(dim-1)), "form_param" (1) and
+ * b_dj = lambda ((u - D) . n) delta_dj + mu ((u - D)_d n_j + (u - D)_j n_d) (:379-386, 437-443, 501-509, 565-573,
+ * 628-636); lambda and mu are evaluated at the side points (constants, closed forms or deck strings).  Not built, and
+ * refused with MHA_ERR_INVALID: "use crystal elasticity", "Biot", "use Lame parameters" = 0, the thermoelastic term of
+ * an "e" variable on the block (:1001-1011), MHA_BC_INTERFACE, mha_compute_flux, the stress output, 1-D.             */
+#define MHA_PHYSICS_LINEARELASTICITY 6
 int mha_physics_select(mha_context *ctx, int physics_id);
 #define MHA_FUNC_CONSTANT 0
 #define MHA_FUNC_IP_ARRAY 1     /* dev pointer to [E][numip] f64                    */
@@ -359,6 +374,9 @@ int mha_workset_compute_residual(mha_context *ctx, int compute_jacobian, const d
 #define MHA_BC_FLUX 3
 #define MHA_BC_INTERFACE 5 /* thermal: the weak-Dirichlet branch with the trace, the function "aux e <sidename>", as data (thermal.cpp:227-243) */
 #define MHA_BC_DIRICHLET 4 /* strong condition (mha_add_dirichlet_group): nothing in mha_assemble_boundary, see mha_set_dirichlet */
+/* linearelasticity: a group's type holds for ALL components of the side (linearelasticity.cpp:244-672); MHA_BC_NEUMANN reads
+ * "Neumann dx|dy|dz <sidename>" (:361-371), MHA_BC_WEAK_DIRICHLET "Dirichlet dx|dy|dz <sidename>" (:372-390, 430-447, 493-513,
+ * 557-577, 620-640); MHA_BC_INTERFACE and mha_compute_flux are refused on that block (see MHA_PHYSICS_LINEARELASTICITY). */
 /* shallowwaterHybridized side types (bcs(H_num, side): "interface", "Far-field", "Slip",
  * shallowwaterHybridized.cpp:286-300, 612-620): the group's entries are element sides (all four sides of every
  * element for the HDG interior problem); the trace state comes from the functions "aux H <sidename>",

@@ -38,7 +38,9 @@ MASS_ON_THE_FLY, MASS_LOCAL, MASS_DATABASE, MASS_DATABASE_SPARSE = 0, 1, 2, 3
 SWH_INTERFACE, SWH_FARFIELD, SWH_SLIP = 0, 1, 2
 BASIS_HGRAD, BASIS_HVOL, BASIS_HDIV = 0, 1, 2
 PHYSICS_IDS = {"thermal": 1, "porousMixed": 2, "navierstokes": 3, "shallowwaterHybridized": 4,
-               "navierstokes+thermal": 5}  # 5: `modules: navierstokes, thermal` on one block (ux, pr, uy[, uz], e)
+               "navierstokes+thermal": 5,  # 5: `modules: navierstokes, thermal` on one block (ux, pr, uy[, uz], e)
+               "linearelasticity": 6}  # dx, dy[, dz] (HGRAD)
+PHYSICS_LINEARELASTICITY = 6
 PATH_POINT_ENGINE = 4
 PATH_ROW_GATHER = 5
 BC_NEUMANN, BC_WEAK_DIRICHLET, BC_FLUX = 1, 2, 3

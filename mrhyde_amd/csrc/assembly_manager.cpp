@@ -368,6 +368,14 @@ void AssemblyManager::selectPhysics(int physics_id) {
                 "navierstokes+thermal needs the " << dim_ + 2 << " HGRAD variables ux, pr, uy" << (dim_ == 3 ? ", uz" : "")
                                                    << ", e, in that order");
   }
+  else if (physics_id == MHA_PHYSICS_LINEARELASTICITY) {
+    bool ok = static_cast<int>(vars_.size()) == dim_;
+    for (const auto &vi : vars_) ok = ok && vi.type == MHA_BASIS_HGRAD;
+    MHA_REQUIRE(ok, MHA_ERR_INVALID,
+                "linearelasticity needs the " << dim_ << " HGRAD variables dx, dy" << (dim_ == 3 ? ", dz" : "")
+                                              << ", in that order (the thermoelastic term of an 'e' variable on the block "
+                                                 "is not built)");
+  }
   physics_id_ = physics_id;
   physics_ = import_physics(physics_id, dim_);
   physics_->defineFunctions(functions_);
@@ -1398,9 +1406,18 @@ int AssemblyManager::addBoundaryGroup(const std::string &sidename, int bc_type, 
     MHA_REQUIRE(side_ids[k] >= 0 && side_ids[k] < side_ref_.nsides, MHA_ERR_INVALID,
                 "boundary entry " << k << ": local side id " << side_ids[k] << " out of range");
   }
-  MHA_REQUIRE(thermal_boundary_supported(n_, side_ref_.nqs), MHA_ERR_INVALID,
-              "boundary terms are not available for " << n_ << " dofs per element with " << side_ref_.nqs
-                                                      << " side integration points");
+  if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY) {
+    MHA_REQUIRE(bc_type == MHA_BC_NEUMANN || bc_type == MHA_BC_WEAK_DIRICHLET, MHA_ERR_INVALID,
+                "linearelasticity: boundary groups are MHA_BC_NEUMANN (traction) or MHA_BC_WEAK_DIRICHLET; the interface "
+                "condition (MHA_BC_INTERFACE) is not built");
+    MHA_REQUIRE(linearelasticity_boundary_supported(dim_, n_, side_ref_.nqs), MHA_ERR_INVALID,
+                "linearelasticity boundary terms are not available for " << n_ << " dofs per element with "
+                                                                         << side_ref_.nqs << " side integration points");
+  } else {
+    MHA_REQUIRE(thermal_boundary_supported(n_, side_ref_.nqs), MHA_ERR_INVALID,
+                "boundary terms are not available for " << n_ << " dofs per element with " << side_ref_.nqs
+                                                        << " side integration points");
+  }
   std::unique_ptr<BoundaryGroupData> g(new BoundaryGroupData());
   g->sidename = sidename;
   g->bc_type = bc_type;
@@ -1570,6 +1587,10 @@ void AssemblyManager::assembleBoundary(int flags, const double *u, const double 
     for (const auto &g : boundary_groups_)
       MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX, MHA_ERR_INVALID,
                   "navierstokes+thermal: thermal boundary groups are not built for the coupled block (group '" << g->sidename << "')");
+  if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY)
+    for (const auto &g : boundary_groups_)
+      MHA_REQUIRE(g->bc_type != MHA_BC_INTERFACE, MHA_ERR_INVALID,
+                  "linearelasticity: the interface condition (MHA_BC_INTERFACE) is not built (group '" << g->sidename << "')");
   timedBegin();
   for (size_t gi = 0; gi < boundary_groups_.size(); ++gi) {
     const auto &g = boundary_groups_[gi];

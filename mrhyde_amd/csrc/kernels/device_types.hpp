@@ -302,6 +302,15 @@ struct SwhBoundaryDev {
   FuncDesc farfield[3];         // "Far-field H|Hux|Huy <side>"
 };
 
+// linearelasticity::boundaryResidual on a boundary group (kernels/linearelasticity_boundary.hip)
+struct LeBoundaryDev {
+  // f[0..2]: "Neumann d<x|y|z> <side>" or "Dirichlet d<x|y|z> <side>" at the side points ([num][nqs] arrays, ...);
+  // f[3], f[4]: "lambda", "mu" at the side points (constants, closed forms or deck strings)
+  FuncDesc f[5];
+  double penalty = 10.0, form_param = 1.0;
+  int plane_stress = 0;        // incplanestress (2-D): the stress with lambda = 2 mu; penalty and b keep lambda
+};
+
 // HDG element of shallowwaterHybridized, side part (kernels/swhdg_element.hip)
 struct SwhElementDev {
   const double *lambda = nullptr;        // [E][24] trace unknowns: variable, HFACE edge (left, bottom, right, top), function

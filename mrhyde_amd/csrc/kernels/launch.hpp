@@ -144,6 +144,11 @@ void launch_swhdg_side(const SwhSideArgs &a, hipStream_t stream);
 void launch_swhdg_boundary(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd, const SwhBoundaryDev &sw,
                            const TimeDev &tm, const ElemOut &out, hipStream_t stream);
 
+// linearelasticity_boundary.hip: linearelasticity::boundaryResidual (traction, weak Dirichlet on all components)
+bool linearelasticity_boundary_supported(int dim, int n, int nqs);
+void launch_linearelasticity_boundary(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd,
+                                      const LeBoundaryDev &le, const TimeDev &tm, const ElemOut &out, hipStream_t stream);
+
 // swhdg_element.hip: HDG element blocks of shallowwaterHybridized (interior + trace unknowns), side part
 void launch_swhdg_element(const BlockDev &b, const SideTablesDev &st, const SwhElementDev &a, const TimeDev &tm,
                           hipStream_t stream);

@@ -243,6 +243,34 @@ __device__ __forceinline__ void navierstokes_thermal_point(const PointArgs<DIM> 
   }
 }
 
+// linearelasticity (reference: src/physics/linearelasticity.cpp:92-240 with computeStress :913-1099, onside = false);
+// myvars {dx, dy[, dz]}; functions {lambda, mu, source dx, source dy, source dz}; p = {incplanestress}.
+// sigma = lambda tr(grad u) I + mu (grad u + grad u^T); row d gets sum_j sigma_dj d_j v - source_d v.  incplanestress
+// (2-D, :990-1000) writes the normal stresses as 4 mu d_x dx + 2 mu d_y dy and its mirror: the Lame form with lambda = 2 mu.
+// No time-derivative term: a transient call scales the operator by alpha_u through the seeding.
+template <int DIM, bool EXPR>
+__device__ __forceinline__ void linearelasticity_point(const PointArgs<DIM> &a, Dual *F) {
+  static_assert(DIM >= 2, "");
+  constexpr int S = 1 + DIM;  // slots per HGRAD variable
+  const PhysParamsDev &pp = *a.pp;
+  auto fn = [&](int k) { return eval_func<DIM, EXPR>(pp.f[k], a.e, a.q, a.nq, a.x); };
+  const double mu = fn(1);
+  const double lam = (DIM == 2 && pp.p[0] != 0.0) ? 2.0 * mu : fn(0);
+  Dual tr = mk(0.0);
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) tr += a.U[d * S + 1 + d];
+  const Dual ltr = tr * lam;
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    F[d * S] = mk(-fn(2 + d));
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) {
+      F[d * S + 1 + j] = (a.U[d * S + 1 + j] + a.U[j * S + 1 + d]) * mu;
+      if (j == d) F[d * S + 1 + j] += ltr;
+    }
+  }
+}
+
 // shallowwaterHybridized (reference: src/physics/shallowwaterHybridized.cpp:113-184 with computeFluxVector(false)
 // :409-480); myvars {H, Hux, Huy} (2-D); functions {source H, source Hux, source Huy}; p = {g}
 template <int DIM, bool EXPR>

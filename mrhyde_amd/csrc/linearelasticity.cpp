@@ -1,0 +1,99 @@
+#include "linearelasticity.hpp"
+
+namespace mha {
+
+linearelasticity::linearelasticity(int dim) {
+  label = "linearelasticity";
+  if (dim == 2) myvars = {"dx", "dy"};  // reference: linearelasticity.cpp:33-40
+  else myvars = {"dx", "dy", "dz"};
+  mybasistypes.assign(myvars.size(), "HGRAD");
+}
+
+// reference: linearelasticity::defineFunctions (linearelasticity.cpp:72-76): lambda 1, mu 0.5, sources 0
+void linearelasticity::defineFunctions(FunctionManager &fm) {
+  functionManager = &fm;
+  auto constant = [](double v) { FuncDesc f; f.kind = MHA_FUNC_CONSTANT; f.amp = v; return f; };
+  if (!fm.has("lambda")) fm.addFunction("lambda", constant(1.0));
+  if (!fm.has("mu")) fm.addFunction("mu", constant(0.5));
+  for (const char *k : {"source dx", "source dy", "source dz"})
+    if (!fm.has(k)) fm.addFunction(k, constant(0.0));
+}
+
+// reference: the constructor's settings (linearelasticity.cpp:42-58).  The options whose terms are not built are
+// accepted at the value that leaves them off and refused otherwise.
+void linearelasticity::setParameter(const std::string &name, double value) {
+  if (name == "incplanestress") incplanestress = value != 0.0;
+  else if (name == "form_param") formparam = value;
+  else if (name == "penalty") penalty = value;
+  else if (name == "use crystal elasticity")
+    MHA_REQUIRE(value == 0.0, MHA_ERR_INVALID, "linearelasticity: 'use crystal elasticity' is not built (CrystalElastic::computeStress)");
+  else if (name == "Biot")
+    MHA_REQUIRE(value == 0.0, MHA_ERR_INVALID, "linearelasticity: 'Biot' (the pressure term of a poroelastic block) is not built");
+  else if (name == "use Lame parameters")
+    MHA_REQUIRE(value != 0.0, MHA_ERR_INVALID,
+                "linearelasticity: 'use Lame parameters' = 0 is not built; give 'lambda' and 'mu'");
+  else PhysicsBase::setParameter(name, value);
+}
+
+// reference: linearelasticity::volumeResidual (linearelasticity.cpp:92-240) as the point function linearelasticity_point
+void linearelasticity::volumeResidual() {
+  MHA_REQUIRE(wkset != nullptr, MHA_ERR_STATE, "linearelasticity::volumeResidual called without a workset");
+  Workset &w = *wkset;
+  BlockDev b = w.dev;
+  b.e_begin = w.first_elem;
+  b.e_count = w.numElem;
+  PhysParamsDev pp;
+  pp.physics = MHA_PHYSICS_LINEARELASTICITY;
+  const char *names[5] = {"lambda", "mu", "source dx", "source dy", "source dz"};
+  for (int k = 0; k < 5; ++k) pp.f[k] = functionManager->evaluate(names[k]);
+  pp.p[0] = incplanestress ? 1.0 : 0.0;
+  launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+}
+
+// reference: linearelasticity::boundaryResidual (linearelasticity.cpp:244-672).  The group's type holds for every
+// component of the side; the data of component d is "Neumann d<x|y|z> <side>" (default 0) or "Dirichlet d<x|y|z> <side>".
+void linearelasticity::boundaryResidual() {
+  MHA_REQUIRE(wkset != nullptr, MHA_ERR_STATE, "linearelasticity::boundaryResidual called without a workset");
+  Workset &w = *wkset;
+  MHA_REQUIRE(w.current_bc != MHA_BC_INTERFACE, MHA_ERR_INVALID,
+              "linearelasticity: the interface condition (MHA_BC_INTERFACE, the multiscale weak Dirichlet) is not built");
+  if (w.current_bc != MHA_BC_NEUMANN && w.current_bc != MHA_BC_WEAK_DIRICHLET) return;
+  const bool weak = w.current_bc == MHA_BC_WEAK_DIRICHLET;
+  for (int v = 1; v < w.layout.nvars; ++v)
+    MHA_REQUIRE(w.layout.card[v] == w.layout.card[0], MHA_ERR_INVALID,
+                "linearelasticity boundary terms need the same order on every component");
+  LeBoundaryDev le;
+  const int dim = w.dimension;
+  for (int d = 0; d < dim; ++d) {
+    const std::string name = std::string(weak ? "Dirichlet " : "Neumann ") + myvars[d] + " " + w.sidename;
+    if (weak) {
+      le.f[d] = functionManager->evaluate(name);
+    } else if (functionManager->has(name)) {
+      le.f[d] = functionManager->evaluate(name);
+    } else {
+      le.f[d].kind = MHA_FUNC_CONSTANT;  // a component without traction data (linearelasticity.cpp:267-284 evaluates
+      le.f[d].amp = 0.0;                 // only what the deck names)
+    }
+    MHA_REQUIRE(!le.f[d].uses_fields, MHA_ERR_INVALID, "boundary data '" << name << "' reads solution fields: not built");
+  }
+  if (weak) {
+    le.f[3] = functionManager->evaluate("lambda");
+    le.f[4] = functionManager->evaluate("mu");
+    MHA_REQUIRE(le.f[3].kind != MHA_FUNC_IP_ARRAY && le.f[4].kind != MHA_FUNC_IP_ARRAY, MHA_ERR_INVALID,
+                "weak Dirichlet needs 'lambda' and 'mu' at the side points: give them as constants, closed forms or deck strings");
+    MHA_REQUIRE(!le.f[3].uses_fields && !le.f[4].uses_fields, MHA_ERR_INVALID,
+                "linearelasticity: 'lambda' and 'mu' that read solution fields are not built");
+  }
+  le.penalty = penalty;
+  le.form_param = formparam;
+  le.plane_stress = incplanestress && dim == 2 ? 1 : 0;
+  BoundaryDev bd = w.bnd;
+  bd.bc_type = w.current_bc;
+  launch_linearelasticity_boundary(w.dev, w.side_tables, bd, le, w.time_dev, w.res, w.stream);
+}
+
+void linearelasticity::computeFlux() {
+  throw Error(MHA_ERR_INVALID, "linearelasticity: computeFlux is not built");
+}
+
+}  // namespace mha
