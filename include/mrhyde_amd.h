@@ -66,7 +66,9 @@ typedef struct mha_block_desc {
                                     navierstokes: dim+1 ("ux","pr","uy"[,"uz"]);
                                     navierstokes + thermal: dim+2
                                     ("ux","pr","uy"[,"uz"],"e");
-                                    linearelasticity: dim ("dx","dy"[,"dz"])     */
+                                    linearelasticity: dim ("dx","dy"[,"dz"]);
+                                    linearelasticity + thermal: dim+1
+                                    ("dx","dy"[,"dz"],"e")                       */
   int basis_type[MHA_MAX_VARS];  /* MHA_BASIS_*, in the module's myvars order    */
   int basis_order[MHA_MAX_VARS]; /* Discretization: order                       */
   int quadrature_degree;         /* Discretization: quadrature (0 => 2*max order,
@@ -136,9 +138,24 @@ int mha_get_graph(mha_context *ctx, int32_t *rowptr_host, int32_t *colind_host);
  * penalty = "penalty" (10) * (lambda + 2 mu) / h, h = (sum of the side weights)^(1/(dim-1)), "form_param" (1) and
  * b_dj = lambda ((u - D) . n) delta_dj + mu ((u - D)_d n_j + (u - D)_j n_d) (:379-386, 437-443, 501-509, 565-573,
  * 628-636); lambda and mu are evaluated at the side points (constants, closed forms or deck strings).  Not built, and
- * refused with MHA_ERR_INVALID: "use crystal elasticity", "Biot", "use Lame parameters" = 0, the thermoelastic term of
- * an "e" variable on the block (:1001-1011), MHA_BC_INTERFACE, mha_compute_flux, the stress output, 1-D.             */
+ * refused with MHA_ERR_INVALID: "use crystal elasticity", "Biot", "use Lame parameters" = 0, an "e" variable on the
+ * block (the thermoelastic term is MHA_PHYSICS_LINEARELASTICITY_THERMAL), MHA_BC_INTERFACE, mha_compute_flux, 1-D.
+ * The stress output is mha_get_derived_values.                                                                    */
 #define MHA_PHYSICS_LINEARELASTICITY 6
+/* linearelasticity + thermal on one block: the reference's `modules: thermal, linearelasticity` (thermoelastic coupling).
+ * Variables dx, dy[, dz], e, all HGRAD, in that order (num_vars = dim + 1; the reference finds them by name); the
+ * displacements share one order, e may have its own.  linearelasticity::setWorkset (linearelasticity.cpp:860-906) finds
+ * e_num, computeStress (:913-1276) then adds -alpha_T (e - T_ambient) c to every normal stress, c = 3 lambda + 2 mu
+ * (:1024-1034, 1074-1084) and c = 5 mu under "incplanestress" in 2-D (:1001-1011).  The e row is thermal's
+ * (thermal.cpp:125-163): rho cp de/dt - source, kappa grad e, (b . grad e) with "include advection".  Functions: "lambda"
+ * (1), "mu" (0.5), "source dx|dy|dz" (0), "thermal source" (0), "thermal diffusion" (1), "specific heat" (1), "density"
+ * (1), "bx", "by", "bz" (0).  Parameters: "incplanestress", "T_ambient" (0), "alpha_T" (1e-6) (:54-58), "include
+ * advection"; "form_param" and "penalty" are accepted and unused.  Volume terms on every assembly path, strong Dirichlet
+ * rows, the generic "Flux" condition and MHA_BC_NEUMANN (traction on the displacements; e order <= displacement order).
+ * Refused with MHA_ERR_INVALID: MHA_BC_WEAK_DIRICHLET and MHA_BC_INTERFACE groups (their side stress needs the
+ * thermoelastic term at the side points), thermal's own boundary groups on e, mha_compute_flux,
+ * MHA_ASSEMBLE_DETERMINISTIC, deck strings that read solution fields, and the options the plain block refuses.       */
+#define MHA_PHYSICS_LINEARELASTICITY_THERMAL 7
 int mha_physics_select(mha_context *ctx, int physics_id);
 #define MHA_FUNC_CONSTANT 0
 #define MHA_FUNC_IP_ARRAY 1     /* dev pointer to [E][numip] f64                    */
@@ -376,7 +393,8 @@ int mha_workset_compute_residual(mha_context *ctx, int compute_jacobian, const d
 #define MHA_BC_DIRICHLET 4 /* strong condition (mha_add_dirichlet_group): nothing in mha_assemble_boundary, see mha_set_dirichlet */
 /* linearelasticity: a group's type holds for ALL components of the side (linearelasticity.cpp:244-672); MHA_BC_NEUMANN reads
  * "Neumann dx|dy|dz <sidename>" (:361-371), MHA_BC_WEAK_DIRICHLET "Dirichlet dx|dy|dz <sidename>" (:372-390, 430-447, 493-513,
- * 557-577, 620-640); MHA_BC_INTERFACE and mha_compute_flux are refused on that block (see MHA_PHYSICS_LINEARELASTICITY). */
+ * 557-577, 620-640); MHA_BC_INTERFACE and mha_compute_flux are refused on that block (see MHA_PHYSICS_LINEARELASTICITY).
+ * linearelasticity + thermal: MHA_BC_NEUMANN only (traction on dx, dy[, dz]; see MHA_PHYSICS_LINEARELASTICITY_THERMAL). */
 /* shallowwaterHybridized side types (bcs(H_num, side): "interface", "Far-field", "Slip",
  * shallowwaterHybridized.cpp:286-300, 612-620): the group's entries are element sides (all four sides of every
  * element for the HDG interior problem); the trace state comes from the functions "aux H <sidename>",
@@ -441,6 +459,21 @@ int mha_assemble_boundary(mha_context *ctx, int flags, const double *u_dev, cons
  * factor alpha_u included), dflux_daux_dev[num][nqs] with respect to the aux value at the point.                     */
 int mha_compute_flux(mha_context *ctx, int group_id, const double *u_dev, const double *u_prev_dev, const double *u_stage_dev,
                      double *flux_dev, double *dflux_du_dev, double *dflux_daux_dev);
+/* Derived quantities of the block's module at the volume integration points.
+ * replaces: linearelasticity::getDerivedNames / getDerivedValues (src/physics/linearelasticity.cpp:1289-1360).
+ * mha_num_derived: 2 on MHA_PHYSICS_LINEARELASTICITY and MHA_PHYSICS_LINEARELASTICITY_THERMAL, 0 on every other module
+ * (-1: bad context).  mha_derived_name: "VM stress", "MAG stress" (:1292-1293); NULL out of range.                     */
+int mha_num_derived(mha_context *ctx);
+const char *mha_derived_name(mha_context *ctx, int k);
+/* getDerivedValues (:1301-1360) for all elements of the block in one launch: computeStress (:913-1099, with the
+ * thermoelastic term on the coupled block) from the solution u_dev as given (no stage seeding), "lambda" and "mu"
+ * evaluated at the integration points at the current time (mha_set_time); then
+ *   2-D (:1326-1338): VM = sqrt(sxx^2 - sxx syy + syy^2 + 3 sxy^2), MAG = sqrt(sxx^2 + syy^2)
+ *   3-D (:1339-1354): VM = sqrt(((sxx-syy)^2 + (syy-szz)^2 + (szz-sxx)^2) / 2 + 3 (sxy^2 + syz^2 + szx^2)),
+ *                     MAG = sqrt(sxx^2 + syy^2 + szz^2)   (the normal components only, as the reference has it).
+ * vm_dev[E][nq], mag_dev[E][nq], stress_dev[E][nq][dim][dim]; each may be NULL and is then skipped.  Every module
+ * without derived quantities refuses the call with MHA_ERR_INVALID.                                                 */
+int mha_get_derived_values(mha_context *ctx, const double *u_dev, double *vm_dev, double *mag_dev, double *stress_dev);
 int mha_boundary_update(mha_context *ctx, int group_id);
 int mha_boundary_view(mha_context *ctx, int group_id, const char *name, void **dev_ptr, int64_t extents[4],
                       int *rank);

@@ -32,6 +32,7 @@ EXPORTS = [
     "mha_set_element_data", "mha_import_mesh_data", "mha_set_parameter_vector", "mha_closest_points", "mha_kl_expansion",
     "mha_kl_indices", "mha_swhdg_set_subgrids", "mha_swhdg_condensed_subgrid", "mha_swhdg_subgrid_blocks",
     "mha_mesh_swhdg_subgrids_sizes", "mha_mesh_swhdg_subgrids",
+    "mha_num_derived", "mha_derived_name", "mha_get_derived_values",
 ]
 KL_MAX_TERMS = 8  # MHA_KL_MAX_TERMS: KL roots per direction the kernels evaluate
 MASS_ON_THE_FLY, MASS_LOCAL, MASS_DATABASE, MASS_DATABASE_SPARSE = 0, 1, 2, 3
@@ -39,8 +40,10 @@ SWH_INTERFACE, SWH_FARFIELD, SWH_SLIP = 0, 1, 2
 BASIS_HGRAD, BASIS_HVOL, BASIS_HDIV = 0, 1, 2
 PHYSICS_IDS = {"thermal": 1, "porousMixed": 2, "navierstokes": 3, "shallowwaterHybridized": 4,
                "navierstokes+thermal": 5,  # 5: `modules: navierstokes, thermal` on one block (ux, pr, uy[, uz], e)
-               "linearelasticity": 6}  # dx, dy[, dz] (HGRAD)
+               "linearelasticity": 6,  # dx, dy[, dz] (HGRAD)
+               "linearelasticity+thermal": 7}  # `modules: thermal, linearelasticity` on one block (dx, dy[, dz], e)
 PHYSICS_LINEARELASTICITY = 6
+PHYSICS_LINEARELASTICITY_THERMAL = 7
 PATH_POINT_ENGINE = 4
 PATH_ROW_GATHER = 5
 BC_NEUMANN, BC_WEAK_DIRICHLET, BC_FLUX = 1, 2, 3
@@ -934,6 +937,26 @@ class Block:
         lib.mha_compute_flux.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
         _check(lib.mha_compute_flux(self._h, int(group_id), _ptr(u), _ptr(u_prev), _ptr(u_stage), _ptr(flux), _ptr(dflux_du),
                                     _ptr(dflux_daux)))
+
+    def derived_names(self):
+        """<module>::getDerivedNames: ["VM stress", "MAG stress"] on the two elasticity blocks, [] on every other."""
+        lib = load_library()
+        lib.mha_derived_name.restype = C.c_char_p
+        lib.mha_derived_name.argtypes = [C.c_void_p, C.c_int]
+        return [lib.mha_derived_name(self._h, k).decode() for k in range(lib.mha_num_derived(self._h))]
+
+    def derived_values(self, u, stress=None):
+        """<module>::getDerivedValues at the integration points of every element from the solution u as given (CUDA
+        tensor [nrows]).  -> {name: CUDA tensor [E, numip]}; stress: optional CUDA tensor [E, numip, dim, dim] that
+        receives the full stress tensor."""
+        import torch
+        lib = load_library()
+        lib.mha_get_derived_values.argtypes = [C.c_void_p] * 5
+        shape = (self.info("num_elems"), self.info("num_ip"))
+        vm = torch.empty(shape, dtype=torch.float64, device=u.device)  # (the kernel writes every entry)
+        mag = torch.empty(shape, dtype=torch.float64, device=u.device)
+        _check(lib.mha_get_derived_values(self._h, _ptr(u), _ptr(vm), _ptr(mag), _ptr(stress)))
+        return {"VM stress": vm, "MAG stress": mag}
 
     def add_flux_group(self, sidename, varname, elem_ids, side_ids):
         """The "Flux" condition of PhysicsInterface::fluxConditions for one variable; data = function "Flux <var> <side>"."""

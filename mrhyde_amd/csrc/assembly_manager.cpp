@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "linearelasticity.hpp"
 #include "porous_data.hpp"
 #include "porous_plan.hpp"
 #include "row_owner_plan.hpp"
@@ -374,7 +375,17 @@ void AssemblyManager::selectPhysics(int physics_id) {
     MHA_REQUIRE(ok, MHA_ERR_INVALID,
                 "linearelasticity needs the " << dim_ << " HGRAD variables dx, dy" << (dim_ == 3 ? ", dz" : "")
                                               << ", in that order (the thermoelastic term of an 'e' variable on the block "
-                                                 "is not built)");
+                                                 "is the module linearelasticity+thermal, MHA_PHYSICS_LINEARELASTICITY_THERMAL)");
+  }
+  else if (physics_id == MHA_PHYSICS_LINEARELASTICITY_THERMAL) {
+    bool ok = static_cast<int>(vars_.size()) == dim_ + 1 && (dim_ == 2 || dim_ == 3);
+    for (const auto &vi : vars_) ok = ok && vi.type == MHA_BASIS_HGRAD;
+    MHA_REQUIRE(ok, MHA_ERR_INVALID,
+                "linearelasticity+thermal needs the " << dim_ + 1 << " HGRAD variables dx, dy" << (dim_ == 3 ? ", dz" : "")
+                                                       << ", e, in that order");
+    for (int d = 1; d < dim_; ++d)
+      MHA_REQUIRE(vars_[d].order == vars_[0].order, MHA_ERR_INVALID,
+                  "linearelasticity+thermal needs the same order on every displacement component (e may have its own)");
   }
   physics_id_ = physics_id;
   physics_ = import_physics(physics_id, dim_);
@@ -1406,7 +1417,17 @@ int AssemblyManager::addBoundaryGroup(const std::string &sidename, int bc_type, 
     MHA_REQUIRE(side_ids[k] >= 0 && side_ids[k] < side_ref_.nsides, MHA_ERR_INVALID,
                 "boundary entry " << k << ": local side id " << side_ids[k] << " out of range");
   }
-  if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY) {
+  if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY_THERMAL) {
+    MHA_REQUIRE(bc_type == MHA_BC_NEUMANN, MHA_ERR_INVALID,
+                "linearelasticity+thermal: boundary groups are MHA_BC_NEUMANN (traction on the displacements); weak-Dirichlet "
+                "and interface groups (MHA_BC_WEAK_DIRICHLET, MHA_BC_INTERFACE: their side stress needs the thermoelastic "
+                "term at the side points) and thermal's groups on e are not built for the coupled block");
+    MHA_REQUIRE(vars_[0].order == order_, MHA_ERR_INVALID,
+                "linearelasticity+thermal: traction groups need the order of e not above the displacements'");
+    MHA_REQUIRE(linearelasticity_boundary_supported(dim_, dim_ * vars_[0].card, side_ref_.nqs), MHA_ERR_INVALID,
+                "linearelasticity boundary terms are not available for " << vars_[0].card << " dofs per component with "
+                                                                         << side_ref_.nqs << " side integration points");
+  } else if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY) {
     MHA_REQUIRE(bc_type == MHA_BC_NEUMANN || bc_type == MHA_BC_WEAK_DIRICHLET, MHA_ERR_INVALID,
                 "linearelasticity: boundary groups are MHA_BC_NEUMANN (traction) or MHA_BC_WEAK_DIRICHLET; the interface "
                 "condition (MHA_BC_INTERFACE) is not built");
@@ -1587,6 +1608,16 @@ void AssemblyManager::assembleBoundary(int flags, const double *u, const double 
     for (const auto &g : boundary_groups_)
       MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX, MHA_ERR_INVALID,
                   "navierstokes+thermal: thermal boundary groups are not built for the coupled block (group '" << g->sidename << "')");
+  if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY_THERMAL)
+    for (const auto &g : boundary_groups_) {
+      MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX || g->bc_type == MHA_BC_NEUMANN, MHA_ERR_INVALID,
+                  "linearelasticity+thermal: only traction (MHA_BC_NEUMANN) groups are built for the coupled block (group '"
+                      << g->sidename << "')");
+      // a Neumann side with data for e is thermal's own condition (thermal.cpp:188-216): not run, and not passed over
+      MHA_REQUIRE(g->bc_type != MHA_BC_NEUMANN || !functions_.has("Neumann e " + g->sidename), MHA_ERR_INVALID,
+                  "linearelasticity+thermal: thermal's boundary groups on e are not built for the coupled block ('Neumann e "
+                      << g->sidename << "' is set); a Neumann group is traction on the displacements");
+    }
   if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY)
     for (const auto &g : boundary_groups_)
       MHA_REQUIRE(g->bc_type != MHA_BC_INTERFACE, MHA_ERR_INVALID,
@@ -1619,6 +1650,51 @@ void AssemblyManager::assembleBoundary(int flags, const double *u, const double 
     wkset_.res.crs_vals = compute_jacobian ? crs_vals : nullptr;
     physics_->boundaryResidual();
   }
+  timedEnd();
+}
+
+const char *AssemblyManager::derivedName(int k) {
+  if (!physics_) return nullptr;
+  derived_names_ = physics_->getDerivedNames();
+  return k >= 0 && k < static_cast<int>(derived_names_.size()) ? derived_names_[k].c_str() : nullptr;
+}
+
+// reference: linearelasticity::getDerivedValues (linearelasticity.cpp:1301-1360): computeStress with "lambda" and "mu" at
+// the integration points, then "VM stress" and "MAG stress".  One launch over all elements; the solution is read as given.
+void AssemblyManager::getDerivedValues(const double *u, double *vm, double *mag, double *stress) {
+  requireReady(false);
+  MHA_REQUIRE(!physics_->getDerivedNames().empty(), MHA_ERR_INVALID,
+              "physics module '" << physics_->label << "' has no derived quantities (the stress output is linearelasticity's)");
+  MHA_REQUIRE(u != nullptr, MHA_ERR_INVALID, "solution vector is null");
+  LeStressDev a;
+  for (int d = 1; d < dim_; ++d)
+    MHA_REQUIRE(vars_[d].card == vars_[0].card, MHA_ERR_INVALID,
+                "the stress output needs the same order on every displacement component");
+  const VarPointsDev pu = varPoints(0, false);
+  a.card_u = pu.card;
+  a.grad_u = pu.grad;
+  a.orient = pu.orient;
+  a.lam = functions_.evaluate("lambda");
+  a.mu = functions_.evaluate("mu");
+  if (const auto *le = dynamic_cast<const linearelasticity *>(physics_.get())) {
+    a.plane_stress = le->incplanestress && dim_ == 2 ? 1 : 0;
+  } else if (const auto *te = dynamic_cast<const linearelasticityThermal *>(physics_.get())) {
+    const VarPointsDev pe = varPoints(dim_, false);
+    a.card_e = pe.card;
+    a.off_e = pe.var_off;
+    a.val_e = pe.val;
+    a.plane_stress = te->incplanestress && dim_ == 2 ? 1 : 0;
+    a.alpha_T = te->alpha_T;
+    a.T_ambient = te->T_ambient;
+  } else {
+    MHA_REQUIRE(false, MHA_ERR_INVALID, "physics module '" << physics_->label << "' has no stress output");
+  }
+  a.u = u;
+  a.vm = vm;
+  a.mag = mag;
+  a.stress = stress;
+  timedBegin();
+  launch_linearelasticity_stress(blockDev(), a, stream_);
   timedEnd();
 }
 

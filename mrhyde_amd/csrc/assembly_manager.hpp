@@ -88,6 +88,10 @@ class AssemblyManager {
   int numBoundaryGroups() const { return static_cast<int>(boundary_groups_.size()); }
   void assembleBoundary(int flags, const double *u, const double *u_prev, const double *u_stage, double *res,
                         double *crs_vals);
+  // <module>::getDerivedNames / getDerivedValues (linearelasticity.cpp:1289-1360) on all elements of the block
+  int numDerived() const { return physics_ ? static_cast<int>(physics_->getDerivedNames().size()) : 0; }
+  const char *derivedName(int k);
+  void getDerivedValues(const double *u, double *vm, double *mag, double *stress);
   void computeFlux(int group, const double *u, const double *u_prev, const double *u_stage, double *flux, double *dflux_du,
                    double *dflux_daux);
   void boundaryUpdate(int group);
@@ -139,6 +143,7 @@ class AssemblyManager {
   std::vector<VarInfo> vars_;
   bool single_hgrad_ = true;  // the thermal kernels of thermal_*.hip need one HGRAD variable
   int physics_id_ = 0;
+  std::vector<std::string> derived_names_;  // storage behind derivedName()
   VarLayoutDev layout_;
   DeviceBuffer<double> d_slot_tables_;
   DeviceBuffer<int8_t> d_orient_;

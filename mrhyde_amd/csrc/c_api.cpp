@@ -240,6 +240,14 @@ int mha_get_mass(mha_context *ctx, const double *masswts_host, double *local_mas
   return guarded([&] { mgr(ctx).getMass(masswts_host, local_mass_dev); });
 }
 
+int mha_num_derived(mha_context *ctx) { return ctx ? ctx->mgr.numDerived() : -1; }
+
+const char *mha_derived_name(mha_context *ctx, int k) { return ctx ? ctx->mgr.derivedName(k) : nullptr; }
+
+int mha_get_derived_values(mha_context *ctx, const double *u, double *vm, double *mag, double *stress) {
+  return guarded([&] { mgr(ctx).getDerivedValues(u, vm, mag, stress); });
+}
+
 int mha_scatter_local(mha_context *ctx, const double *local_J, const double *local_res, double *res,
                       double *crs_vals) {
   return guarded([&] { mgr(ctx).scatterLocal(local_J, local_res, res, crs_vals); });

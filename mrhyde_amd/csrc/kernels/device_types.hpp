@@ -309,6 +309,23 @@ struct LeBoundaryDev {
   FuncDesc f[5];
   double penalty = 10.0, form_param = 1.0;
   int plane_stress = 0;        // incplanestress (2-D): the stress with lambda = 2 mu; penalty and b keep lambda
+  int disp_card = 0;           // > 0: the coupled linearelasticity + thermal block (dofs of one displacement component;
+                               // the element's b.n dofs end with those of e): traction on the displacement rows only
+};
+
+// linearelasticity::getDerivedValues on all elements of a block (kernels/linearelasticity_stress.hip)
+struct LeStressDev {
+  int card_u = 0;                  // dofs of one displacement component (the block's first dim variables)
+  int card_e = 0, off_e = 0;       // the coupled block: dofs of e and its first dof in (variable, dof) order; 0: no e
+  const double *grad_u = nullptr;  // [card_u][nq][dim] reference gradients of the displacement basis
+  const double *val_e = nullptr;   // [card_e][nq] reference values of e's basis
+  const int8_t *orient = nullptr;  // [E][n] basis signs or null
+  FuncDesc lam, mu;                // "lambda", "mu" at the integration points
+  int plane_stress = 0;            // incplanestress (2-D)
+  double alpha_T = 0.0, T_ambient = 0.0;
+  const double *u = nullptr;       // [nrows] the solution, as given
+  double *vm = nullptr, *mag = nullptr;  // [E][nq] "VM stress", "MAG stress" (null: skipped)
+  double *stress = nullptr;              // [E][nq][dim][dim] (null: skipped)
 };
 
 // HDG element of shallowwaterHybridized, side part (kernels/swhdg_element.hip)

@@ -149,6 +149,9 @@ bool linearelasticity_boundary_supported(int dim, int n, int nqs);
 void launch_linearelasticity_boundary(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd,
                                       const LeBoundaryDev &le, const TimeDev &tm, const ElemOut &out, hipStream_t stream);
 
+// linearelasticity_stress.hip: linearelasticity::getDerivedValues (stress tensor, "VM stress", "MAG stress")
+void launch_linearelasticity_stress(const BlockDev &b, const LeStressDev &a, hipStream_t stream);
+
 // swhdg_element.hip: HDG element blocks of shallowwaterHybridized (interior + trace unknowns), side part
 void launch_swhdg_element(const BlockDev &b, const SideTablesDev &st, const SwhElementDev &a, const TimeDev &tm,
                           hipStream_t stream);

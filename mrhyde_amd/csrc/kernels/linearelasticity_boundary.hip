@@ -39,12 +39,14 @@ __host__ __device__ inline int le_entry_doubles(int dim, int card, int nqs) {
   return (card * nqs * (dim + 2) + n + nqs * (dim * dim + le_point_doubles(dim)) + (n + 1) / 2 + 1) & ~1;
 }
 
-template <int DIM, int TPE>
-__global__ __launch_bounds__(kLeThreads) void linearelasticity_boundary_kernel(BlockDev b, SideTablesDev st, BoundaryDev bd,
-                                                                               LeBoundaryDev le, TimeDev tm, ElemOut out) {
+// TE: the entry is an element of the coupled linearelasticity + thermal block -- its displacement rows are the first
+// DIM * le.disp_card of the b.n dofs; traction only (the host refuses everything else on that block)
+template <int DIM, int TPE, bool TE>
+__device__ __forceinline__ void le_boundary_entry(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd,
+                                                  const LeBoundaryDev &le, const TimeDev &tm, const ElemOut &out) {
   constexpr int NN = 1 << DIM, PT = le_point_doubles(DIM), NG = kLeThreads / TPE;
   extern __shared__ double smem[];
-  const int n = b.n, card = n / DIM, nqs = st.nqs;
+  const int n = TE ? DIM * le.disp_card : b.n, card = n / DIM, nqs = st.nqs;
   const int grp = threadIdx.x / TPE, t = threadIdx.x % TPE;
   double *s_N = smem + grp * le_entry_doubles(DIM, card, nqs);
   double *s_G = s_N + card * nqs, *s_gn = s_G + card * nqs * DIM;
@@ -54,8 +56,8 @@ __global__ __launch_bounds__(kLeThreads) void linearelasticity_boundary_kernel(B
   const int k = blockIdx.x * NG + grp;
   const bool active = k < bd.num;  // inactive groups still take part in the block barriers
   const int e = active ? bd.elem[k] : 0, s = active ? bd.side[k] : 0;
-  const bool weak = bd.bc_type == MHA_BC_WEAK_DIRICHLET;
-  const int32_t *L = b.lids + (size_t)e * n;
+  const bool weak = !TE && bd.bc_type == MHA_BC_WEAK_DIRICHLET;
+  const int32_t *L = b.lids + (size_t)e * b.n;
 
   // A. side geometry, coefficients and data (thread = (side point, function): ONE inlined copy of the deck-string
   // interpreter, which costs registers per copy); gather + seeding value (thread = (component, dof))
@@ -200,6 +202,19 @@ __global__ __launch_bounds__(kLeThreads) void linearelasticity_boundary_kernel(B
   }
 }
 
+template <int DIM, int TPE>
+__global__ __launch_bounds__(kLeThreads) void linearelasticity_boundary_kernel(BlockDev b, SideTablesDev st, BoundaryDev bd,
+                                                                               LeBoundaryDev le, TimeDev tm, ElemOut out) {
+  le_boundary_entry<DIM, TPE, false>(b, st, bd, le, tm, out);
+}
+
+template <int DIM, int TPE>
+__global__ __launch_bounds__(kLeThreads) void linearelasticity_thermal_traction_kernel(BlockDev b, SideTablesDev st,
+                                                                                       BoundaryDev bd, LeBoundaryDev le,
+                                                                                       TimeDev tm, ElemOut out) {
+  le_boundary_entry<DIM, TPE, true>(b, st, bd, le, tm, out);
+}
+
 }  // namespace
 
 bool linearelasticity_boundary_supported(int dim, int n, int nqs) {
@@ -209,13 +224,17 @@ bool linearelasticity_boundary_supported(int dim, int n, int nqs) {
 void launch_linearelasticity_boundary(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd,
                                       const LeBoundaryDev &le, const TimeDev &tm, const ElemOut &out, hipStream_t stream) {
   if (bd.num <= 0) return;
-  MHA_REQUIRE(linearelasticity_boundary_supported(b.dim, b.n, st.nqs), MHA_ERR_INVALID,
+  const bool te = le.disp_card > 0;  // coupled block: traction on the displacement rows
+  const int rows = te ? b.dim * le.disp_card : b.n;
+  MHA_REQUIRE(!te || (bd.bc_type == MHA_BC_NEUMANN && rows <= b.n), MHA_ERR_INVALID,
+              "linearelasticity+thermal: only traction (MHA_BC_NEUMANN) groups are built");
+  MHA_REQUIRE(linearelasticity_boundary_supported(b.dim, rows, st.nqs), MHA_ERR_INVALID,
               "linearelasticity boundary kernel: equal-order components with at most " << kLeMaxCard << " dofs each and "
                                                                                       << kLeMaxQ << " side points (got "
-                                                                                      << b.n << " dofs per element, "
+                                                                                      << rows << " displacement dofs per element, "
                                                                                       << st.nqs << " side points)");
-  const int card = b.n / b.dim;
-  const bool wave_per_entry = b.n <= 32;
+  const int card = rows / b.dim;
+  const bool wave_per_entry = rows <= 32;
   const int per_wg = wave_per_entry ? kLeThreads / 64 : 1;
   const size_t lds = sizeof(double) * per_wg * le_entry_doubles(b.dim, card, st.nqs);
   const int grid = (bd.num + per_wg - 1) / per_wg;
@@ -223,7 +242,15 @@ void launch_linearelasticity_boundary(const BlockDev &b, const SideTablesDev &st
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kLeThreads), lds, stream, b, st, bd, le, tm, out);
     MHA_HIP(hipGetLastError());
   };
-  if (b.dim == 2) {
+  if (te) {
+    if (b.dim == 2) {
+      if (wave_per_entry) go(linearelasticity_thermal_traction_kernel<2, 64>);
+      else go(linearelasticity_thermal_traction_kernel<2, kLeThreads>);
+    } else {
+      if (wave_per_entry) go(linearelasticity_thermal_traction_kernel<3, 64>);
+      else go(linearelasticity_thermal_traction_kernel<3, kLeThreads>);
+    }
+  } else if (b.dim == 2) {
     if (wave_per_entry) go(linearelasticity_boundary_kernel<2, 64>);
     else go(linearelasticity_boundary_kernel<2, kLeThreads>);
   } else {

@@ -9,6 +9,7 @@
 #pragma once
 #include "device_math.hpp"
 #include "dual.hpp"
+#include "linearelasticity_stress.hpp"
 
 namespace mha {
 
@@ -268,6 +269,43 @@ __device__ __forceinline__ void linearelasticity_point(const PointArgs<DIM> &a, 
       F[d * S + 1 + j] = (a.U[d * S + 1 + j] + a.U[j * S + 1 + d]) * mu;
       if (j == d) F[d * S + 1 + j] += ltr;
     }
+  }
+}
+
+// linearelasticity + thermal on one block (the thermoelastic coupling; reference: linearelasticity::setWorkset
+// linearelasticity.cpp:860-906 finds e_num when the block has a variable "e", computeStress :913-1276 then subtracts
+// alpha_T (e - T_ambient) c from the normal stresses); myvars {dx, dy[, dz], e}; functions {lambda, mu, source dx,
+// source dy, source dz, thermal source, thermal diffusion, specific heat, density, bx, by, bz};
+// p = {incplanestress, T_ambient, alpha_T, include advection}.  Displacement rows: those of linearelasticity_point with the
+// stress of le_stress (linearelasticity_stress.hpp); energy row: thermal's without have_nsvel (thermal.cpp:125-163).  The
+// e-columns of the displacement rows come out of the same forward-AD pass; the energy row reads no displacement.  Its own
+// function: the two modules' point functions above compile exactly as without it.
+template <int DIM, bool EXPR>
+__device__ __forceinline__ void linearelasticity_thermal_point(const PointArgs<DIM> &a, Dual *F) {
+  static_assert(DIM >= 2, "");
+  constexpr int S = 1 + DIM, eb = DIM * S;  // slots per HGRAD variable; first slot of e
+  const PhysParamsDev &pp = *a.pp;
+  auto fn = [&](int k) { return eval_func<DIM, EXPR>(pp.f[k], a.e, a.q, a.nq, a.x); };
+  const double lam = fn(0), mu = fn(1);
+  Dual gu[DIM * DIM], sig[DIM * DIM];
+#pragma unroll
+  for (int d = 0; d < DIM; ++d)
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) gu[d * DIM + j] = a.U[d * S + 1 + j];
+  le_stress<DIM, Dual>(gu, &a.U[eb], lam, mu, pp.p[0] != 0.0, pp.p[2], pp.p[1], sig);
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    F[d * S] = mk(-fn(2 + d));
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) F[d * S + 1 + j] = sig[d * DIM + j];
+  }
+  const double f = fn(5), kap = fn(6), cp = fn(7), rho = fn(8);
+  F[eb] = a.Ud[eb] * (rho * cp) - f;
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) F[eb + 1 + d] = a.U[eb + 1 + d] * kap;
+  if (pp.p[3] != 0.0) {
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) F[eb] += a.U[eb + 1 + d] * fn(9 + d);
   }
 }
 

@@ -70,6 +70,14 @@ struct Layout<MHA_PHYSICS_LINEARELASTICITY, DIM> {
   __host__ __device__ static constexpr int type(int) { return MHA_BASIS_HGRAD; }
 };
 
+// linearelasticity + thermal: dx, dy[, dz], e
+template <int DIM>
+struct Layout<MHA_PHYSICS_LINEARELASTICITY_THERMAL, DIM> {
+  static constexpr int nvars = DIM + 1, NS = (DIM + 1) * (1 + DIM);
+  static_assert(NS <= kMaxSlots, "");
+  __host__ __device__ static constexpr int type(int) { return MHA_BASIS_HGRAD; }
+};
+
 template <int DIM>
 struct Layout<MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED, DIM> {
   static constexpr int nvars = 3, NS = 3 * (1 + DIM);
@@ -370,6 +378,7 @@ __global__ __launch_bounds__(kEngineThreads) void point_engine_kernel(BlockDev b
       else if constexpr (PHYS == MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED) swhdg_point<DIM, (EXPR != 0)>(pa, F);
       else if constexpr (PHYS == MHA_PHYSICS_NAVIERSTOKES_THERMAL) navierstokes_thermal_point<DIM, (EXPR != 0)>(pa, F);
       else if constexpr (PHYS == MHA_PHYSICS_LINEARELASTICITY) linearelasticity_point<DIM, (EXPR != 0)>(pa, F);
+      else if constexpr (PHYS == MHA_PHYSICS_LINEARELASTICITY_THERMAL) linearelasticity_thermal_point<DIM, (EXPR != 0)>(pa, F);
       else navierstokes_point<DIM, (EXPR != 0)>(pa, F);
 #pragma unroll
       for (int v = 0; v < L::nvars; ++v) {
@@ -846,6 +855,8 @@ void launch_point_engine(const BlockDev &b, const VarLayoutDev &vl, const PhysPa
     case 30 + MHA_PHYSICS_NAVIERSTOKES_THERMAL: launch_typed<3, MHA_PHYSICS_NAVIERSTOKES_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
     case 20 + MHA_PHYSICS_LINEARELASTICITY: launch_typed<2, MHA_PHYSICS_LINEARELASTICITY>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
     case 30 + MHA_PHYSICS_LINEARELASTICITY: launch_typed<3, MHA_PHYSICS_LINEARELASTICITY>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 20 + MHA_PHYSICS_LINEARELASTICITY_THERMAL: launch_typed<2, MHA_PHYSICS_LINEARELASTICITY_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 30 + MHA_PHYSICS_LINEARELASTICITY_THERMAL: launch_typed<3, MHA_PHYSICS_LINEARELASTICITY_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
     case 20 + MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED: launch_typed<2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
     default: MHA_REQUIRE(false, MHA_ERR_INVALID, "no point-engine kernel for physics " << pp.physics << " in " << b.dim << "-D");
   }

@@ -96,4 +96,97 @@ void linearelasticity::computeFlux() {
   throw Error(MHA_ERR_INVALID, "linearelasticity: computeFlux is not built");
 }
 
+// ---- linearelasticity + thermal on one block ---------------------------------------------------------------------
+linearelasticityThermal::linearelasticityThermal(int dim) {
+  label = "linearelasticity+thermal";
+  if (dim == 2) myvars = {"dx", "dy", "e"};  // linearelasticity.cpp:33-40 and thermal.cpp:31
+  else myvars = {"dx", "dy", "dz", "e"};
+  mybasistypes.assign(myvars.size(), "HGRAD");
+}
+
+// both modules' defineFunctions (linearelasticity.cpp:72-76, thermal.cpp:52-63) on one function manager
+void linearelasticityThermal::defineFunctions(FunctionManager &fm) {
+  functionManager = &fm;
+  auto constant = [](double v) { FuncDesc f; f.kind = MHA_FUNC_CONSTANT; f.amp = v; return f; };
+  if (!fm.has("mu")) fm.addFunction("mu", constant(0.5));
+  for (const char *k : {"source dx", "source dy", "source dz", "thermal source", "bx", "by", "bz"})
+    if (!fm.has(k)) fm.addFunction(k, constant(0.0));
+  for (const char *k : {"lambda", "thermal diffusion", "specific heat", "density"})
+    if (!fm.has(k)) fm.addFunction(k, constant(1.0));
+}
+
+void linearelasticityThermal::setParameter(const std::string &name, double value) {
+  if (name == "incplanestress") incplanestress = value != 0.0;
+  else if (name == "form_param") formparam = value;
+  else if (name == "penalty") penalty = value;
+  else if (name == "T_ambient") T_ambient = value;
+  else if (name == "alpha_T") alpha_T = value;
+  else if (name == "include advection") have_advection = value != 0.0;
+  else if (name == "use crystal elasticity")
+    MHA_REQUIRE(value == 0.0, MHA_ERR_INVALID, "linearelasticity+thermal: 'use crystal elasticity' is not built (CrystalElastic::computeStress)");
+  else if (name == "Biot")
+    MHA_REQUIRE(value == 0.0, MHA_ERR_INVALID, "linearelasticity+thermal: 'Biot' (the pressure term of a poroelastic block) is not built");
+  else if (name == "use Lame parameters")
+    MHA_REQUIRE(value != 0.0, MHA_ERR_INVALID,
+                "linearelasticity+thermal: 'use Lame parameters' = 0 is not built; give 'lambda' and 'mu'");
+  else PhysicsBase::setParameter(name, value);
+}
+
+// linearelasticity::volumeResidual with e_num >= 0 and thermal::volumeResidual as ONE point function
+// (linearelasticity_thermal_point): the e-columns of the displacement rows come out of the same forward-AD pass
+void linearelasticityThermal::volumeResidual() {
+  MHA_REQUIRE(wkset != nullptr, MHA_ERR_STATE, "linearelasticity+thermal::volumeResidual called without a workset");
+  Workset &w = *wkset;
+  for (int v = 1; v + 1 < w.layout.nvars; ++v)
+    MHA_REQUIRE(w.layout.card[v] == w.layout.card[0], MHA_ERR_INVALID,
+                "linearelasticity+thermal needs the same order on every displacement component");
+  BlockDev b = w.dev;
+  b.e_begin = w.first_elem;
+  b.e_count = w.numElem;
+  PhysParamsDev pp;
+  pp.physics = MHA_PHYSICS_LINEARELASTICITY_THERMAL;
+  const char *names[12] = {"lambda", "mu", "source dx", "source dy", "source dz", "thermal source",
+                           "thermal diffusion", "specific heat", "density", "bx", "by", "bz"};
+  static_assert(kMaxFuncs >= 12, "the coupled module names twelve functions");
+  for (int k = 0; k < 12; ++k) pp.f[k] = functionManager->evaluate(names[k]);
+  pp.p[0] = incplanestress ? 1.0 : 0.0;
+  pp.p[1] = T_ambient;
+  pp.p[2] = alpha_T;
+  pp.p[3] = have_advection ? 1.0 : 0.0;
+  launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+}
+
+// Traction (linearelasticity.cpp:361-371, 419-429, 482-492, 546-556, 609-619) reads no stress: the plain block's kernel
+// on the displacement rows of the coupled element.  Everything else on a side is refused (AssemblyManager::addBoundaryGroup
+// has refused it already unless the group was added before the module was selected).
+void linearelasticityThermal::boundaryResidual() {
+  MHA_REQUIRE(wkset != nullptr, MHA_ERR_STATE, "linearelasticity+thermal::boundaryResidual called without a workset");
+  Workset &w = *wkset;
+  MHA_REQUIRE(w.current_bc == MHA_BC_NEUMANN, MHA_ERR_INVALID,
+              "linearelasticity+thermal: boundary groups are MHA_BC_NEUMANN (traction on the displacements); weak-Dirichlet "
+              "and interface groups and thermal's groups on e are not built for the coupled block");
+  MHA_REQUIRE(!functionManager->has("Neumann e " + w.sidename), MHA_ERR_INVALID,
+              "linearelasticity+thermal: thermal's boundary groups on e are not built for the coupled block");
+  const int dim = w.dimension;
+  LeBoundaryDev le;
+  for (int d = 0; d < dim; ++d) {
+    const std::string name = std::string("Neumann ") + myvars[d] + " " + w.sidename;
+    if (functionManager->has(name)) {
+      le.f[d] = functionManager->evaluate(name);
+    } else {
+      le.f[d].kind = MHA_FUNC_CONSTANT;
+      le.f[d].amp = 0.0;
+    }
+    MHA_REQUIRE(!le.f[d].uses_fields, MHA_ERR_INVALID, "boundary data '" << name << "' reads solution fields: not built");
+  }
+  le.disp_card = w.layout.card[0];
+  BoundaryDev bd = w.bnd;
+  bd.bc_type = w.current_bc;
+  launch_linearelasticity_boundary(w.dev, w.side_tables, bd, le, w.time_dev, w.res, w.stream);
+}
+
+void linearelasticityThermal::computeFlux() {
+  throw Error(MHA_ERR_INVALID, "linearelasticity+thermal: computeFlux is not built for the coupled block");
+}
+
 }  // namespace mha

@@ -77,6 +77,8 @@ class PhysicsBase {
   virtual void setParameterVector(const std::string &name, const double *, int) {
     throw Error(MHA_ERR_INVALID, "physics module '" + label + "' has no parameter vector '" + name + "'");
   }
+  // reference: getDerivedNames (physicsBase.hpp); the values are AssemblyManager::getDerivedValues
+  virtual std::vector<std::string> getDerivedNames() const { return {}; }
   // true when the coefficients differ from element to element in a way the geometry database cannot see
   virtual bool heterogeneous() const { return false; }
 

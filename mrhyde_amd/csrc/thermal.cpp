@@ -552,6 +552,7 @@ void shallowwaterHybridized::boundaryResidual() {
 std::unique_ptr<PhysicsBase> import_physics(int physics_id, int dim) {
   if (physics_id == MHA_PHYSICS_NAVIERSTOKES_THERMAL) return std::unique_ptr<PhysicsBase>(new navierstokesThermal(dim));
   if (physics_id == MHA_PHYSICS_LINEARELASTICITY) return std::unique_ptr<PhysicsBase>(new linearelasticity(dim));
+  if (physics_id == MHA_PHYSICS_LINEARELASTICITY_THERMAL) return std::unique_ptr<PhysicsBase>(new linearelasticityThermal(dim));
   if (physics_id == MHA_PHYSICS_THERMAL) return std::unique_ptr<PhysicsBase>(new thermal());
   if (physics_id == MHA_PHYSICS_POROUS_MIXED) return std::unique_ptr<PhysicsBase>(new porousMixed());
   if (physics_id == MHA_PHYSICS_NAVIERSTOKES) return std::unique_ptr<PhysicsBase>(new navierstokes());
