@@ -156,6 +156,29 @@ int mha_get_graph(mha_context *ctx, int32_t *rowptr_host, int32_t *colind_host);
  * thermoelastic term at the side points), thermal's own boundary groups on e, mha_compute_flux,
  * MHA_ASSEMBLE_DETERMINISTIC, deck strings that read solution fields, and the options the plain block refuses.       */
 #define MHA_PHYSICS_LINEARELASTICITY_THERMAL 7
+/* cdr, convection-diffusion-reaction (src/physics/cdr.cpp): one HGRAD variable c (:22-23), 2-D and 3-D.  Volume terms
+ * (:62-142): (c_t + v . grad c + reaction - source) v + diffusion / (density * specific heat) grad c . grad v; no
+ * density * specific heat on the time derivative.  Functions and the reference's defaults (:40-48): "source" (0),
+ * "diffusion" (1), "specific heat" (1), "density" (1), "reaction" (1), "xvel", "yvel", "zvel" (1 each); "SUPG tau" (0) is
+ * accepted and unused, as in the reference (evaluated :82, read by no term; computeTau :186-207 has no caller).  Every
+ * function may be a constant, an array, a closed form, a deck string in the coordinates or a deck string that reads the
+ * solution fields c, grad(c)[x|y|z], c_t and other named functions (reaction: "0.5*c*c"): the Jacobian then holds the
+ * derivative of the string.  boundaryResidual and computeFlux are empty in the reference (:147-164): boundary groups on
+ * the block add nothing, mha_compute_flux returns zeros.  Runs on the point engine (MHA_PATH_AUTO / _ROW_GATHER /
+ * _POINT_ENGINE / _LOCAL_THEN_SCATTER); MHA_PATH_ROW_OWNER and MHA_ASSEMBLE_DETERMINISTIC are refused.  1-D is refused. */
+/* (ids 8 and 9, stated relative to the last id of the list above) */
+#define MHA_PHYSICS_CDR (MHA_PHYSICS_LINEARELASTICITY_THERMAL + 1)
+/* The reference's `modules: navier stokes, cdr` on ONE block: ux, pr, uy[, uz], c, all HGRAD, each with its own order
+ * (num_vars = dim + 2).  The rows of navierstokes (navierstokes.cpp:82-849) and the row of cdr (cdr.cpp:62-142) with no
+ * built-in coupling term: the coupling is what cdr's functions read, e.g. xvel = "ux", yvel = "uy".  Functions: "source
+ * ux|pr|uy|uz", "viscosity" (navierstokes.cpp:68-74), "source", "diffusion", "specific heat", "reaction", "xvel", "yvel",
+ * "zvel", "SUPG tau" (cdr.cpp:40-48), and "density", ONE function read by both modules (functionManager.cpp:48-68).
+ * "source pr" is read by no term.  Parameters: useSUPG, usePSPG, fix_uz_offsets.  cdr's functions may read the solution
+ * fields of the block; navierstokes' own ("source u*", "density", "viscosity") may not (MHA_ERR_INVALID, by name).
+ * Refused with MHA_ERR_INVALID: boundary groups of the modules, mha_compute_flux, MHA_PATH_ROW_OWNER,
+ * MHA_ASSEMBLE_DETERMINISTIC, and the 3-D Q2/Q1/Q2/Q2/Q2 element (its LDS need).  Strong Dirichlet rows and the generic
+ * "Flux" condition work per variable as on every block.                                                             */
+#define MHA_PHYSICS_NAVIERSTOKES_CDR (MHA_PHYSICS_LINEARELASTICITY_THERMAL + 2)
 int mha_physics_select(mha_context *ctx, int physics_id);
 #define MHA_FUNC_CONSTANT 0
 #define MHA_FUNC_IP_ARRAY 1     /* dev pointer to [E][numip] f64                    */
@@ -483,7 +506,8 @@ int mha_boundary_view(mha_context *ctx, int group_id, const char *name, void **d
  * point engine, MHA_PATH_ROW_OWNER is refused); navierstokes: "useSUPG", "usePSPG"
  * (navierstokes.cpp:45-46) and "fix_uz_offsets": the reference scatters the 3-D uz momentum
  * block through uy's offsets (navierstokes.cpp:688); 0 (default) reproduces that, 1 uses uz's;
- * shallowwaterHybridized: "g" (shallowwaterHybridized.cpp:72, default 9.81).                     */
+ * shallowwaterHybridized: "g" (shallowwaterHybridized.cpp:72, default 9.81); navierstokes + cdr: navierstokes' three;
+ * cdr: none.                                                                                      */
 /* porousMixed (porousMixed.cpp:46-120) also takes: "use permeability data" (Kinv_xx = Kinv_yy = Kinv_zz = 1 / data(elem, 0)
  * from the block's element data, in place of the Kinv_* functions, updatePerm :550-563; total_mobility still divides);
  * "use KL expansion" (Kinv_dd divided by exp(KL_dd), a Karhunen-Loeve field evaluated at every integration point,

@@ -42,8 +42,13 @@ PHYSICS_IDS = {"thermal": 1, "porousMixed": 2, "navierstokes": 3, "shallowwaterH
                "navierstokes+thermal": 5,  # 5: `modules: navierstokes, thermal` on one block (ux, pr, uy[, uz], e)
                "linearelasticity": 6,  # dx, dy[, dz] (HGRAD)
                "linearelasticity+thermal": 7}  # `modules: thermal, linearelasticity` on one block (dx, dy[, dz], e)
+# cdr: c (HGRAD), convection-diffusion-reaction, its functions may read the solution fields;
+# navierstokes+cdr: `modules: navier stokes, cdr` on one block (ux, pr, uy[, uz], c)
+PHYSICS_IDS.update({"cdr": 8, "navierstokes+cdr": 9})
 PHYSICS_LINEARELASTICITY = 6
 PHYSICS_LINEARELASTICITY_THERMAL = 7
+PHYSICS_CDR = 8
+PHYSICS_NAVIERSTOKES_CDR = 9
 PATH_POINT_ENGINE = 4
 PATH_ROW_GATHER = 5
 BC_NEUMANN, BC_WEAK_DIRICHLET, BC_FLUX = 1, 2, 3

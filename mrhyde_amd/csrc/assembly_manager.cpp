@@ -387,6 +387,16 @@ void AssemblyManager::selectPhysics(int physics_id) {
       MHA_REQUIRE(vars_[d].order == vars_[0].order, MHA_ERR_INVALID,
                   "linearelasticity+thermal needs the same order on every displacement component (e may have its own)");
   }
+  else if (physics_id == MHA_PHYSICS_CDR)
+    MHA_REQUIRE(expect({MHA_BASIS_HGRAD}) && (dim_ == 2 || dim_ == 3), MHA_ERR_INVALID,
+                "cdr needs one HGRAD variable (c) in 2-D or 3-D");
+  else if (physics_id == MHA_PHYSICS_NAVIERSTOKES_CDR) {
+    bool ok = static_cast<int>(vars_.size()) == dim_ + 2 && (dim_ == 2 || dim_ == 3);
+    for (const auto &vi : vars_) ok = ok && vi.type == MHA_BASIS_HGRAD;
+    MHA_REQUIRE(ok, MHA_ERR_INVALID,
+                "navierstokes+cdr needs the " << dim_ + 2 << " HGRAD variables ux, pr, uy" << (dim_ == 3 ? ", uz" : "")
+                                               << ", c, in that order");
+  }
   physics_id_ = physics_id;
   physics_ = import_physics(physics_id, dim_);
   physics_->defineFunctions(functions_);
@@ -1410,6 +1420,9 @@ int AssemblyManager::addBoundaryGroup(const std::string &sidename, int bc_type, 
   MHA_REQUIRE(physics_id_ != MHA_PHYSICS_NAVIERSTOKES_THERMAL, MHA_ERR_INVALID,
               "navierstokes+thermal: thermal boundary groups (Neumann, weak Dirichlet, interface on e) are not built for "
               "the coupled block; strong Dirichlet rows and the generic Flux condition are");
+  MHA_REQUIRE(physics_id_ != MHA_PHYSICS_NAVIERSTOKES_CDR, MHA_ERR_INVALID,
+              "navierstokes+cdr: boundary groups of the modules (Neumann, weak Dirichlet, interface) are not built for the "
+              "coupled block; strong Dirichlet rows and the generic Flux condition are");
   prepareSideTables();
   for (int k = 0; k < num; ++k) {
     MHA_REQUIRE(elem_ids[k] >= 0 && elem_ids[k] < nelem_, MHA_ERR_INVALID,
@@ -1608,6 +1621,10 @@ void AssemblyManager::assembleBoundary(int flags, const double *u, const double 
     for (const auto &g : boundary_groups_)
       MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX, MHA_ERR_INVALID,
                   "navierstokes+thermal: thermal boundary groups are not built for the coupled block (group '" << g->sidename << "')");
+  if (physics_id_ == MHA_PHYSICS_NAVIERSTOKES_CDR)
+    for (const auto &g : boundary_groups_)
+      MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX, MHA_ERR_INVALID,
+                  "navierstokes+cdr: boundary groups of the modules are not built for the coupled block (group '" << g->sidename << "')");
   if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY_THERMAL)
     for (const auto &g : boundary_groups_) {
       MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX || g->bc_type == MHA_BC_NEUMANN, MHA_ERR_INVALID,

@@ -192,7 +192,8 @@ struct BoundaryViewsDev {
 };
 
 // ---- multi-variable blocks (kernels/point_engine.hip) -------------------------------------------------------------
-// kMaxFuncs: the coupled navierstokes + thermal module names twelve functions.  PhysParamsDev travels by value as a kernel
+// kMaxFuncs: the coupled navierstokes + thermal module names twelve functions (navierstokes + cdr thirteen in 3-D: it
+// leaves out "source pr", which no term reads, rather than widen every kernel's argument block).  PhysParamsDev travels by value as a kernel
 // argument (80 B per FuncDesc): the point engine's argument block is 1 808 B with twelve (1 488 B with eight), of the
 // 4 096 B a HIP kernel may take
 constexpr int kMaxVars = 8, kMaxSlots = 24, kMaxFuncs = 12;

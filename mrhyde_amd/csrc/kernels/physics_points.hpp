@@ -7,6 +7,8 @@
 // Slot numbering: variables in the module's myvars order; HGRAD -> [value, d/dx, d/dy(, d/dz)], HVOL -> [value],
 // HDIV -> [v_x, v_y(, v_z), div].  The integration weight is applied by the engine.
 #pragma once
+#include <type_traits>
+
 #include "device_math.hpp"
 #include "dual.hpp"
 #include "linearelasticity_stress.hpp"
@@ -242,6 +244,84 @@ __device__ __forceinline__ void navierstokes_thermal_point(const PointArgs<DIM> 
 #pragma unroll
     for (int d = 0; d < DIM; ++d) F[eb] += a.U[eb + 1 + d] * fn(9 + d);
   }
+}
+
+// cdr, convection-diffusion-reaction (reference: src/physics/cdr.cpp:62-142); myvars {c}; functions {source, diffusion,
+// specific heat, density, reaction, xvel, yvel, zvel} with the reference's defaults 0, 1, 1, 1, 1, 1, 1, 1 (:40-47).
+//   value slot       c_t + v . grad c + reaction - source      (no rho cp on the time derivative, :104 / :117 / :131)
+//   gradient slot d  diffusion / (density specific heat) d_d c
+// "SUPG tau" is evaluated by the reference and never used (:82 against :96-140), computeTau (:186-207) has no caller:
+// neither is here.  cdr_row is the row of c on any block: cb = first slot of c; COUPLED picks the function table of
+// navierstokes_cdr_point below.  EXPR as for thermal_point; with 2 EVERY function goes through func_dual, so a function
+// may read c, grad(c)[x|y|z], c_t, the other variables of a coupled block, the coordinates and other named functions
+// (reaction: '0.5*c*c', xvel: 'ux').  The functions are evaluated in a loop that is NOT unrolled: the Dual interpreter
+// is inlined once, and the kernel keeps to the scratch it may use (require_modest_scratch).
+template <bool COUPLED>
+__device__ __forceinline__ constexpr int cdr_func_index(int k) {
+  // k: 0 source, 1 diffusion, 2 specific heat, 3 density, 4 reaction, 5.. xvel, yvel, zvel
+  return !COUPLED ? k : k == 0 ? 1 : k == 3 ? 4 : k < 3 ? 5 + k : 4 + k;
+}
+template <int DIM, int EXPR, bool COUPLED>
+__device__ __forceinline__ void cdr_row(const PointArgs<DIM> &a, int cb, Dual *F) {
+  constexpr int NF = 5 + DIM;
+  using T = std::conditional_t<EXPR == 2, Dual, double>;
+  const PhysParamsDev &pp = *a.pp;
+  T fv[NF];
+  if constexpr (EXPR == 2) {
+#pragma nounroll
+    for (int k = 0; k < NF; ++k) fv[k] = func_dual<DIM>(pp.f[cdr_func_index<COUPLED>(k)], a);
+  } else if constexpr (EXPR == 1) {
+#pragma nounroll
+    for (int k = 0; k < NF; ++k) fv[k] = eval_func<DIM, true>(pp.f[cdr_func_index<COUPLED>(k)], a.e, a.q, a.nq, a.x);
+  } else {
+#pragma unroll
+    for (int k = 0; k < NF; ++k) fv[k] = eval_func<DIM, (EXPR != 0)>(pp.f[cdr_func_index<COUPLED>(k)], a.e, a.q, a.nq, a.x);
+  }
+  Dual f = a.Ud[cb] + fv[4] - fv[0];
+  const T kd = fv[1] / (fv[3] * fv[2]);
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    f += a.U[cb + 1 + d] * fv[5 + d];
+    F[cb + 1 + d] = a.U[cb + 1 + d] * kd;
+  }
+  F[cb] = f;
+}
+template <int DIM, int EXPR>
+__device__ __forceinline__ void cdr_point(const PointArgs<DIM> &a, Dual *F) {
+  cdr_row<DIM, EXPR, false>(a, 0, F);
+}
+
+// navierstokes + cdr on one block (the reference's `modules: navier stokes, cdr`); myvars {ux, pr, uy[, uz], c}.  No
+// built-in coupling term: the rows of navierstokes_point and the row of cdr_row side by side; the coupling is whatever
+// cdr's functions read (xvel: 'ux' gives the c-row / ux-column entries as the derivative of a deck string).
+// functions {source ux, source (cdr's), source uy, source uz, density, viscosity, diffusion, specific heat, reaction,
+// xvel, yvel, zvel}: navierstokes' table with cdr's source where "source pr" would be -- navierstokes_point never reads
+// that entry, and with it the coupled module would name 13 functions where the table holds 12 -- then cdr's own.
+// "density" is ONE function read by both modules (FunctionManager::addFunction keeps the first tree of a name).
+// p = navierstokes' {useSUPG, usePSPG, fix_uz_offsets}.  With EXPR = 2 only cdr's functions are Duals; navierstokes'
+// own are plain values (the host refuses a field-reading one by name).
+template <int DIM, int EXPR>
+__device__ __forceinline__ void navierstokes_cdr_point(const PointArgs<DIM> &a, Dual *F) {
+  if constexpr (EXPR == 0) {
+    navierstokes_point<DIM, false>(a, F);
+  } else {
+    // navierstokes' five functions (source ux / uy / uz, density, viscosity) in a loop that is not unrolled -- one
+    // inlined interpreter instead of five -- then handed to navierstokes_point as constants
+    PhysParamsDev nsp;
+    double v[5];
+#pragma nounroll
+    for (int k = 0; k < 5; ++k) v[k] = eval_func<DIM, true>(a.pp->f[k == 0 ? 0 : k + 1], a.e, a.q, a.nq, a.x);
+    nsp.f[0].amp = v[0];
+#pragma unroll
+    for (int k = 1; k < 5; ++k) nsp.f[k + 1].amp = v[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) nsp.p[k] = a.pp->p[k];
+    static_assert(MHA_FUNC_CONSTANT == 0, "a default FuncDesc is a constant");
+    PointArgs<DIM> an = a;
+    an.pp = &nsp;
+    navierstokes_point<DIM, false>(an, F);
+  }
+  cdr_row<DIM, EXPR, true>(a, (DIM + 1) * (1 + DIM), F);
 }
 
 // linearelasticity (reference: src/physics/linearelasticity.cpp:92-240 with computeStress :913-1099, onside = false);

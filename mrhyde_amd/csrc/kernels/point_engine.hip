@@ -78,6 +78,21 @@ struct Layout<MHA_PHYSICS_LINEARELASTICITY_THERMAL, DIM> {
   __host__ __device__ static constexpr int type(int) { return MHA_BASIS_HGRAD; }
 };
 
+// cdr: c
+template <int DIM>
+struct Layout<MHA_PHYSICS_CDR, DIM> {
+  static constexpr int nvars = 1, NS = 1 + DIM;
+  __host__ __device__ static constexpr int type(int) { return MHA_BASIS_HGRAD; }
+};
+
+// navierstokes + cdr on one block: ux, pr, uy[, uz], c
+template <int DIM>
+struct Layout<MHA_PHYSICS_NAVIERSTOKES_CDR, DIM> {
+  static constexpr int nvars = 2 + DIM, NS = (2 + DIM) * (1 + DIM);
+  static_assert(NS <= kMaxSlots, "");
+  __host__ __device__ static constexpr int type(int) { return MHA_BASIS_HGRAD; }
+};
+
 template <int DIM>
 struct Layout<MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED, DIM> {
   static constexpr int nvars = 3, NS = 3 * (1 + DIM);
@@ -175,7 +190,7 @@ __host__ __device__ inline size_t engine_group_doubles(const VarLayoutDev &vl, i
 // element and only wave-level synchronisation inside the element loop; TPE = 512: the whole workgroup, block barriers).
 // NQ1 = integration points per direction when it is 2 or 3 (the loops over points then have compile-time bounds and
 // the compiler batches their LDS loads), 0 = taken from the layout at run time.
-template <int DIM, int PHYS, int TPE, int NQ1, int EXPR>  // EXPR: 0 / 1 deck strings / 2 deck strings that read the solution fields (thermal)
+template <int DIM, int PHYS, int TPE, int NQ1, int EXPR>  // EXPR: 0 / 1 deck strings / 2 deck strings that read the solution fields (thermal, cdr, navierstokes+cdr)
                                                           // / 3 porousMixed with heterogeneous permeability (no deck strings)
 __global__ __launch_bounds__(kEngineThreads) void point_engine_kernel(BlockDev b, VarLayoutDev vl, PhysParamsDev pp,
                                                                       TimeDev tm, ElemOut out_all,
@@ -379,6 +394,8 @@ __global__ __launch_bounds__(kEngineThreads) void point_engine_kernel(BlockDev b
       else if constexpr (PHYS == MHA_PHYSICS_NAVIERSTOKES_THERMAL) navierstokes_thermal_point<DIM, (EXPR != 0)>(pa, F);
       else if constexpr (PHYS == MHA_PHYSICS_LINEARELASTICITY) linearelasticity_point<DIM, (EXPR != 0)>(pa, F);
       else if constexpr (PHYS == MHA_PHYSICS_LINEARELASTICITY_THERMAL) linearelasticity_thermal_point<DIM, (EXPR != 0)>(pa, F);
+      else if constexpr (PHYS == MHA_PHYSICS_CDR) cdr_point<DIM, EXPR>(pa, F);
+      else if constexpr (PHYS == MHA_PHYSICS_NAVIERSTOKES_CDR) navierstokes_cdr_point<DIM, EXPR>(pa, F);
       else navierstokes_point<DIM, (EXPR != 0)>(pa, F);
 #pragma unroll
       for (int v = 0; v < L::nvars; ++v) {
@@ -808,8 +825,9 @@ void launch_typed(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev
     else go(point_engine_kernel<DIM, PHYS, T, 0, 0>);
   };
   if (pp.physics > 0 && uses_fields(pp)) {
-    // deck strings that read the solution fields: the Dual interpreter; built for the thermal module
-    if constexpr (PHYS == MHA_PHYSICS_THERMAL) {
+    // deck strings that read the solution fields: the Dual interpreter; built for the modules whose point function
+    // has an EXPR = 2 form
+    if constexpr (PHYS == MHA_PHYSICS_THERMAL || PHYS == MHA_PHYSICS_CDR || PHYS == MHA_PHYSICS_NAVIERSTOKES_CDR) {
       if (groups == 8) go(point_engine_kernel<DIM, PHYS, 64, 0, 2>);
       else if (groups == 4) go(point_engine_kernel<DIM, PHYS, 128, 0, 2>);
       else if (groups == 2) go(point_engine_kernel<DIM, PHYS, 256, 0, 2>);
@@ -843,6 +861,7 @@ void launch_typed(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev
 void launch_point_engine(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp, const TimeDev &tm,
                          const ElemOut &out, const void *slot, int slot_bytes, hipStream_t stream) {
   if (b.e_count <= 0) return;
+  static_assert(MHA_PHYSICS_NAVIERSTOKES_CDR < 10, "the switch key holds one decimal digit of module id");
   const int key = b.dim * 10 + (pp.physics < 0 ? -pp.physics : pp.physics);
   switch (key) {
     case 20 + MHA_PHYSICS_THERMAL: launch_typed<2, MHA_PHYSICS_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
@@ -857,6 +876,10 @@ void launch_point_engine(const BlockDev &b, const VarLayoutDev &vl, const PhysPa
     case 30 + MHA_PHYSICS_LINEARELASTICITY: launch_typed<3, MHA_PHYSICS_LINEARELASTICITY>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
     case 20 + MHA_PHYSICS_LINEARELASTICITY_THERMAL: launch_typed<2, MHA_PHYSICS_LINEARELASTICITY_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
     case 30 + MHA_PHYSICS_LINEARELASTICITY_THERMAL: launch_typed<3, MHA_PHYSICS_LINEARELASTICITY_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 20 + MHA_PHYSICS_CDR: launch_typed<2, MHA_PHYSICS_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 30 + MHA_PHYSICS_CDR: launch_typed<3, MHA_PHYSICS_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 20 + MHA_PHYSICS_NAVIERSTOKES_CDR: launch_typed<2, MHA_PHYSICS_NAVIERSTOKES_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 30 + MHA_PHYSICS_NAVIERSTOKES_CDR: launch_typed<3, MHA_PHYSICS_NAVIERSTOKES_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
     case 20 + MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED: launch_typed<2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
     default: MHA_REQUIRE(false, MHA_ERR_INVALID, "no point-engine kernel for physics " << pp.physics << " in " << b.dim << "-D");
   }
