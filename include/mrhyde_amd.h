@@ -300,6 +300,28 @@ int mha_database_get(mha_context *ctx, int32_t *index_host, int32_t *first_users
 #define MHA_MASS_DATABASE_SPARSE 3
 int mha_apply_mass_matrix_free(mha_context *ctx, int mode, const double *masswts_host, const double *mass_dev,
                                mha_sparse3d *sparse, const double *x_dev, double *y_dev);
+/* ---- matrix-free Jacobian products ------------------------------------------------------------------------------
+ * y_dev (+)= A x_dev or, with MHA_APPLY_TRANSPOSE, y_dev (+)= A^T x_dev, where A is the matrix that
+ * mha_assemble_jacres(ctx, MHA_ASSEMBLE_JACOBIAN | MHA_ASSEMBLE_OVERWRITE, MHA_PATH_AUTO, u, u_prev, u_stage, ...) stores in
+ * crs_vals: the volume terms with the block's current time-integration seeding, zero rows where the mesh marks a row
+ * fixed, no mha_apply_dbc_diag -- sign +dR/du (the sign of crs_vals, not the -R of res).  Replaces the product with the
+ * matrix of AssemblyManager::assembleJacRes (a Krylov solver's J x, an adjoint solve's J^T x): neither A nor an element
+ * matrix is formed; the module's point function is evaluated once per integration point (forward) or once per point and
+ * slot (transposed) (kernels/jacobian_apply.hip).  The reference has no counterpart beyond applyMassMatrixFree: its
+ * Jacobian exists as a CRS matrix only.  Every module of the point engine (thermal, porousMixed, navierstokes,
+ * navierstokes+thermal, linearelasticity, linearelasticity+thermal, cdr, navierstokes+cdr, the volume terms of
+ * shallowwaterHybridized); thermal runs through its point function here, as under MHA_PATH_POINT_ENGINE.
+ * x_dev[nrows], y_dev[nrows] (a residual-like overlapped vector: shared rows take the Export(ADD) of res).  The forward
+ * product skips fixed rows of y; the transposed product reads x as zero on fixed rows and writes every row.
+ * flags: MHA_ASSEMBLE_OVERWRITE (y is zeroed on the block's stream first; otherwise accumulated into) and
+ * MHA_APPLY_TRANSPOSE; any other bit, a missing mesh / module / graph and a null x or y give MHA_ERR_INVALID, and so do
+ * the refusals of the modules' own validation (e.g. a deck string that reads solution fields on a module without that
+ * form).  A refused call writes nothing to y.  No allocation and no host synchronisation (beyond mha_set_timing's).
+ * Not built: boundary-group terms (mha_assemble_boundary stays the way to get them: add that small matrix's product),
+ * diag(A), several right-hand sides per call, the HDG element / trace blocks.                                        */
+#define MHA_APPLY_TRANSPOSE 32
+int mha_apply_jacobian(mha_context *ctx, int flags, const double *u_dev, const double *u_prev_dev,
+                       const double *u_stage_dev, const double *x_dev, double *y_dev);
 /* replaces: scatterJac / scatterRes  assemblyManager.cpp:3882-3935, 3943-3978          */
 int mha_scatter_local(mha_context *ctx, const double *local_J_dev, const double *local_res_dev,
                       double *res_dev, double *crs_vals_dev);

@@ -32,10 +32,11 @@ EXPORTS = [
     "mha_set_element_data", "mha_import_mesh_data", "mha_set_parameter_vector", "mha_closest_points", "mha_kl_expansion",
     "mha_kl_indices", "mha_swhdg_set_subgrids", "mha_swhdg_condensed_subgrid", "mha_swhdg_subgrid_blocks",
     "mha_mesh_swhdg_subgrids_sizes", "mha_mesh_swhdg_subgrids",
-    "mha_num_derived", "mha_derived_name", "mha_get_derived_values",
+    "mha_num_derived", "mha_derived_name", "mha_get_derived_values", "mha_apply_jacobian",
 ]
 KL_MAX_TERMS = 8  # MHA_KL_MAX_TERMS: KL roots per direction the kernels evaluate
 MASS_ON_THE_FLY, MASS_LOCAL, MASS_DATABASE, MASS_DATABASE_SPARSE = 0, 1, 2, 3
+ASSEMBLE_OVERWRITE, APPLY_TRANSPOSE = 2, 32  # the flags of mha_apply_jacobian
 SWH_INTERFACE, SWH_FARFIELD, SWH_SLIP = 0, 1, 2
 BASIS_HGRAD, BASIS_HVOL, BASIS_HDIV = 0, 1, 2
 PHYSICS_IDS = {"thermal": 1, "porousMixed": 2, "navierstokes": 3, "shallowwaterHybridized": 4,
@@ -130,6 +131,7 @@ def load_library():
         _lib.mha_swhdg_subgrid_solve.argtypes = ([C.c_void_p] * 7 + [C.c_int, C.c_double, C.c_void_p, C.c_int64] + [C.c_void_p] * 5)
         _lib.mha_database_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.mha_apply_mass_matrix_free.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        _lib.mha_apply_jacobian.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         _lib.mha_num_boundary_groups.argtypes = [C.c_void_p]
         _lib.mha_assemble_boundary.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         _lib.mha_boundary_update.argtypes = [C.c_void_p, C.c_int]
@@ -850,6 +852,12 @@ class Block:
         w = None if masswts is None else _np(masswts, np.float64)
         _check(load_library().mha_apply_mass_matrix_free(self._h, mode, None if w is None else w.ctypes.data_as(C.c_void_p),
                                                          _ptr(mass), None if sparse is None else sparse._h, _ptr(x), _ptr(y)))
+
+    def apply_jacobian(self, u, x, y, transpose=False, overwrite=False, u_prev=None, u_stage=None):
+        """y += A x (transpose: A^T x; overwrite: y = ...) with the matrix assemble_jacres stores -- volume terms, current
+        time-integration seeding, fixed rows zero -- never formed (mha_apply_jacobian)."""
+        flags = (ASSEMBLE_OVERWRITE if overwrite else 0) | (APPLY_TRANSPOSE if transpose else 0)
+        _check(load_library().mha_apply_jacobian(self._h, flags, _ptr(u), _ptr(u_prev), _ptr(u_stage), _ptr(x), _ptr(y)))
 
     def swhdg_condensed_element(self, u, lam, schur=None, gvec=None, du=None, num_singular=None, side_types=None,
                                 farfield=None, u_prev=None, u_stage=None):

@@ -909,6 +909,31 @@ void AssemblyManager::applyMassMatrixFree(int mode, const double *masswts, const
                            maxent, nnz_row, values, columns, d_pos_var_.data(), x, y, stream_);
 }
 
+// y (+)= A x / A^T x with the matrix assembleJacRes stores, through the module's point function: the block, layout,
+// function and time-integration set-up of launchPointEngine, the module's own validation, and the product kernel in
+// place of the element assembly.  The reference has no counterpart beyond applyMassMatrixFree.
+void AssemblyManager::applyJacobian(int flags, const double *u, const double *u_prev, const double *u_stage,
+                                    const double *x, double *y) {
+  MHA_REQUIRE((flags & ~(MHA_ASSEMBLE_OVERWRITE | MHA_APPLY_TRANSPOSE)) == 0, MHA_ERR_INVALID,
+              "mha_apply_jacobian takes MHA_ASSEMBLE_OVERWRITE and MHA_APPLY_TRANSPOSE only (flags " << flags << ")");
+  MHA_REQUIRE(has_mesh_, MHA_ERR_INVALID, "no mesh: call mha_set_mesh first");
+  MHA_REQUIRE(physics_ != nullptr, MHA_ERR_INVALID, "no physics module: call mha_physics_select first");
+  MHA_REQUIRE(has_graph_, MHA_ERR_INVALID, "no CRS graph: call mha_set_graph first");
+  MHA_REQUIRE(x && y, MHA_ERR_INVALID, "null vector");
+  bindState(u, u_prev, u_stage);
+  wkset_.apply.mode = (flags & MHA_APPLY_TRANSPOSE) ? 2 : 1;
+  wkset_.apply.overwrite = (flags & MHA_ASSEMBLE_OVERWRITE) ? 1 : 0;
+  wkset_.apply.x = x;
+  wkset_.apply.y = y;
+  struct Restore {  // a refusal inside the module leaves the workset as an assembly expects it
+    Workset &w;
+    ~Restore() { w.apply.mode = 0; w.use_point_engine = false; }
+  } restore{wkset_};
+  timedBegin();
+  launchPointEngine(0, ElemOut(), 0, nelem_);
+  timedEnd();
+}
+
 // reference: AssemblyManager::getMass / getWeightedMass (assemblyManager.cpp:7776-7925): dense element mass matrices,
 // accumulated (+=) into local_mass[E][n][n] in LID-position order.  Runs the point engine with the value slots as
 // the "flux" (kernels/point_engine.hip, mass mode): the mass matrix is the B^T C B product with C = weights.
@@ -2281,6 +2306,8 @@ int64_t AssemblyManager::info(const std::string &key) const {
   if (key == "dofs_per_elem") return n_;
   if (key == "num_ip") return nq_;
   if (key == "last_path") return last_path_;
+  if (key == "jacobian_apply_lds_bytes") return static_cast<int64_t>(wkset_.apply.lds_bytes);  // last mha_apply_jacobian: LDS per workgroup
+  if (key == "jacobian_apply_waves") return wkset_.apply.waves;  // and its wavefronts (= elements) per workgroup
   if (key == "jacobian_database_mode") return last_db_mode_;  // the last affine row-owner Jacobian replicated one block per pattern
   if (key == "block_pattern_rep_launches") return rep_launches_;  // representative launches of the geometry-database mode so far
   if (key == "affine_shapes") return ro_.ready ? ro_.k1_plan.num_shapes : 0;  // distinct geometry records behind the residual kernel's database index

@@ -53,6 +53,9 @@ class AssemblyManager {
   void databaseGet(int32_t *index, int32_t *first_users) const;
   void applyMassMatrixFree(int mode, const double *masswts, const double *mass, int maxent, const int32_t *nnz_row,
                            const double *values, const int32_t *columns, const double *x, double *y);
+  // y (+)= A x or A^T x with the matrix assembleJacRes stores (volume terms, fixed rows zero), never formed
+  // (kernels/jacobian_apply.hip); flags: MHA_ASSEMBLE_OVERWRITE, MHA_APPLY_TRANSPOSE
+  void applyJacobian(int flags, const double *u, const double *u_prev, const double *u_stage, const double *x, double *y);
   void swhdgElementBlocks(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
                           const uint8_t *side_types, const double *farfield, double *res, double *blocks);
   // SubGridDtN_Solver::nonlinearSolver for HDG elements with element-local interior unknowns (subgridDtN_solver.cpp:909-1041)

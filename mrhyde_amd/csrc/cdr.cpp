@@ -55,7 +55,7 @@ void cdr::volumeResidual() {
   pp.physics = MHA_PHYSICS_CDR;
   const char *names[8] = {"source", "diffusion", "specific heat", "density", "reaction", "xvel", "yvel", "zvel"};
   for (int k = 0; k < 5 + w.dimension; ++k) pp.f[k] = functionManager->evaluate(names[k]);
-  launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+  launch_volume_points(w, b, pp);
 }
 
 void cdr::computeFlux() {
@@ -116,7 +116,7 @@ void navierstokesCdr::volumeResidual() {
   pp.p[0] = useSUPG ? 1.0 : 0.0;
   pp.p[1] = usePSPG ? 1.0 : 0.0;
   pp.p[2] = fix_uz_offsets ? 1.0 : 0.0;
-  launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+  launch_volume_points(w, b, pp);
 }
 
 // neither module has a boundary term here (navierstokes' are not built, cdr's are empty in the reference): a group of the

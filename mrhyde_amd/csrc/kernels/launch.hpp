@@ -189,4 +189,12 @@ void launch_export_unpack_add(const double *src, const int32_t *tgt, int64_t n, 
 void launch_point_engine(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp, const TimeDev &tm,
                          const ElemOut &out, const void *slot, int slot_bytes, hipStream_t stream);
 
+// jacobian_apply.hip: y += A x (transpose == 0) or y += A^T x with A the volume Jacobian the point engine assembles
+// (rows marked fixed are zero), one point-function evaluation per direction instead of an element matrix.
+// overwrite: y[0 .. b.nrows) is zeroed on the stream first -- after every check that can refuse the launch.
+// lds_bytes / waves (may be null): the launch's LDS per workgroup and wavefronts (= elements) per workgroup
+void launch_jacobian_apply(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp, const TimeDev &tm,
+                           const double *x, double *y, int transpose, int overwrite, hipStream_t stream,
+                           size_t *lds_bytes = nullptr, int *waves = nullptr);
+
 }  // namespace mha

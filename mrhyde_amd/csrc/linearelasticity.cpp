@@ -47,7 +47,7 @@ void linearelasticity::volumeResidual() {
   const char *names[5] = {"lambda", "mu", "source dx", "source dy", "source dz"};
   for (int k = 0; k < 5; ++k) pp.f[k] = functionManager->evaluate(names[k]);
   pp.p[0] = incplanestress ? 1.0 : 0.0;
-  launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+  launch_volume_points(w, b, pp);
 }
 
 // reference: linearelasticity::boundaryResidual (linearelasticity.cpp:244-672).  The group's type holds for every
@@ -153,7 +153,7 @@ void linearelasticityThermal::volumeResidual() {
   pp.p[1] = T_ambient;
   pp.p[2] = alpha_T;
   pp.p[3] = have_advection ? 1.0 : 0.0;
-  launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+  launch_volume_points(w, b, pp);
 }
 
 // Traction (linearelasticity.cpp:361-371, 419-429, 482-492, 546-556, 609-619) reads no stress: the plain block's kernel

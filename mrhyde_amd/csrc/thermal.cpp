@@ -154,7 +154,7 @@ void thermal::volumeResidual() {
                     "thermal with 'include advection': give the functions as constants, closed forms or per-point arrays "
                     "(deck strings are evaluated by the caller into an ip array)");
     }
-    launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+    launch_volume_points(w, b, pp);
   } else if (have_advection) {
     throw Error(MHA_ERR_INVALID, "thermal with 'include advection' runs on the point engine (MHA_PATH_AUTO / _ROW_GATHER / _POINT_ENGINE)");
   } else if (w.use_general)
@@ -235,10 +235,10 @@ void porousMixed::volumeResidual() {
   // dense element arrays (row-gather path, mha_compute_local_jacres): the thread-per-element kernel; global outputs
   // (atomic scatter): the point engine.  MHA_POROUS_KERNEL=engine forces the engine.
   static const bool force_engine = [] { const char *m = std::getenv("MHA_POROUS_KERNEL"); return m && m[0] == 'e'; }();
-  if (!force_engine && w.res.res == nullptr && w.res.crs_vals == nullptr)
+  if (!force_engine && !w.apply.mode && w.res.res == nullptr && w.res.crs_vals == nullptr)
     launch_porous_element(b, w.layout, pp, w.time_dev, w.res, w.stream);
   else
-    launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+    launch_volume_points(w, b, pp);
 }
 
 // reference: porousMixed constructor settings (porousMixed.cpp:46-120): "use permeability data", "use KL expansion" and the
@@ -424,7 +424,7 @@ void navierstokes::volumeResidual() {
   pp.p[0] = useSUPG ? 1.0 : 0.0;
   pp.p[1] = usePSPG ? 1.0 : 0.0;
   pp.p[2] = fix_uz_offsets ? 1.0 : 0.0;
-  launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+  launch_volume_points(w, b, pp);
 }
 
 // ---- navierstokes + thermal on one block -------------------------------------------------------------------------
@@ -477,7 +477,7 @@ void navierstokesThermal::volumeResidual() {
   pp.p[3] = T_ambient;
   pp.p[4] = beta;
   pp.p[5] = have_advection ? 1.0 : 0.0;
-  launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+  launch_volume_points(w, b, pp);
 }
 
 // thermal::boundaryResidual / computeFlux act on "e" through kernels written for a one-variable block: out of scope
@@ -526,7 +526,7 @@ void shallowwaterHybridized::volumeResidual() {
   const char *names[3] = {"source H", "source Hux", "source Huy"};
   for (int k = 0; k < 3; ++k) pp.f[k] = functionManager->evaluate(names[k]);
   pp.p[0] = gravity;
-  launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+  launch_volume_points(w, b, pp);
 }
 
 // reference: shallowwaterHybridized::boundaryResidual (:190-263) on the current boundary group; the trace ("aux") state

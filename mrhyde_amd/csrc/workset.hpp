@@ -53,6 +53,15 @@ class Workset {
   // multi-variable point engine (kernels/point_engine.hip): variable/slot layout, orientation signs
   VarLayoutDev layout;
   bool use_point_engine = false;
+  // matrix-free Jacobian product (kernels/jacobian_apply.hip): mode != 0 sends the module's volume terms to it instead
+  // of the element assembly (1: y (+)= A x, 2: y (+)= A^T x); lds_bytes / waves report the launch
+  struct Apply {
+    int mode = 0, overwrite = 0;
+    const double *x = nullptr;
+    double *y = nullptr;
+    size_t lds_bytes = 0;
+    int waves = 0;
+  } apply;
   bool single_hgrad = true;  // basis / basis_grad views exist for single-variable HGRAD blocks only
   hipStream_t stream = nullptr;
   int order = 0, nq1 = 0;
@@ -83,6 +92,17 @@ class Workset {
   DeviceBuffer<double> basis_, basis_grad_, wts_, xyz_[3];
   int views_first_ = -1, views_num_ = 0;
 };
+
+// A module's volume terms on its point function: the element assembly into w.res (kernels/point_engine.hip) or, when the
+// workset carries a product request, y (+)= A x / A^T x with the same Jacobian (kernels/jacobian_apply.hip).
+inline void launch_volume_points(Workset &w, const BlockDev &b, const PhysParamsDev &pp) {
+  if (w.apply.mode) {
+    launch_jacobian_apply(b, w.layout, pp, w.time_dev, w.apply.x, w.apply.y, w.apply.mode == 2, w.apply.overwrite,
+                          w.stream, &w.apply.lds_bytes, &w.apply.waves);
+  } else {
+    launch_point_engine(b, w.layout, pp, w.time_dev, w.res, w.elem_slot, w.elem_slot_bytes, w.stream);
+  }
+}
 
 inline void Workset::update_views() {
   const size_t ne = static_cast<size_t>(numElem), n = dev.n, nq = dev.nq, d = dev.dim;
