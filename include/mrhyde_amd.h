@@ -317,11 +317,39 @@ int mha_apply_mass_matrix_free(mha_context *ctx, int mode, const double *masswts
  * MHA_APPLY_TRANSPOSE; any other bit, a missing mesh / module / graph and a null x or y give MHA_ERR_INVALID, and so do
  * the refusals of the modules' own validation (e.g. a deck string that reads solution fields on a module without that
  * form).  A refused call writes nothing to y.  No allocation and no host synchronisation (beyond mha_set_timing's).
+ * diag(A): mha_jacobian_diagonal; several vectors per call: mha_apply_jacobian_multi (below).
  * Not built: boundary-group terms (mha_assemble_boundary stays the way to get them: add that small matrix's product),
- * diag(A), several right-hand sides per call, the HDG element / trace blocks.                                        */
+ * block diagonals, the HDG element / trace blocks, the wiring into the Newton driver.                                */
 #define MHA_APPLY_TRANSPOSE 32
 int mha_apply_jacobian(mha_context *ctx, int flags, const double *u_dev, const double *u_prev_dev,
                        const double *u_stage_dev, const double *x_dev, double *y_dev);
+/* d_dev[nrows] (+)= diag(A) with the matrix A of mha_apply_jacobian -- volume terms, the current seeding, the sign of
+ * crs_vals, zero on the rows the mesh marks fixed (d is exactly 0 there under MHA_ASSEMBLE_OVERWRITE), no
+ * mha_apply_dbc_diag -- without the matrix: what a Jacobi or Chebyshev smoother of a matrix-free Krylov solve is built
+ * from.  One point-function evaluation per integration point and slot, as in the transposed product; per dof the block
+ * of its own variable is contracted with the dof's basis values on both sides (kernels/jacobian_diagonal.hip).  d is
+ * a residual-like overlapped vector: shared rows take the Export(ADD) of res.  A is zero, and so is d, on fixed rows and
+ * on rows the module leaves empty (pressure without PSPG, the uz rows under the uz-offset quirk): a Jacobi user gives
+ * those a value of their own.  flags: MHA_ASSEMBLE_OVERWRITE only (d is zeroed on the block's stream first; otherwise
+ * accumulated into); any other bit, a missing mesh / module / graph, a null d and the refusals of the modules' own
+ * validation give MHA_ERR_INVALID with d untouched.  No allocation and no host synchronisation.  The reference has no
+ * counterpart.  Not built: block diagonals, boundary-group terms.                                                    */
+int mha_jacobian_diagonal(mha_context *ctx, int flags, const double *u_dev, const double *u_prev_dev,
+                          const double *u_stage_dev, double *d_dev);
+/* Y_k (+)= A X_k or, with MHA_APPLY_TRANSPOSE, A^T X_k for k = 0 .. nvec-1 with the matrix A and the flags of
+ * mha_apply_jacobian.  Vector k is x_dev + k ldx (y_dev + k ldy), nrows entries each -- the layout of a Krylov basis;
+ * ldx, ldy >= nrows.  What does not depend on the vector -- the gather of u, the geometry, the fields of u and, in the
+ * transposed product, the point-function evaluations -- is paid once per launch, and the forward product fills the
+ * lanes the single call leaves idle with the other vectors (kernels/jacobian_apply_multi.hip).  One launch carries up
+ * to MHA_APPLY_MAX_VECTORS vectors (fewer where the LDS of the element shape says so: mha_info
+ * "jacobian_apply_vectors"); any nvec >= 1 is taken, in passes.  Fixed rows as in the single call: the forward product
+ * skips them in every Y_k, the transposed product reads X_k as zero there.  MHA_ASSEMBLE_OVERWRITE zeroes Y_k[0, nrows)
+ * only: the padding between vectors is never written.  nvec < 1, ldx or ldy < nrows, a null pointer and everything
+ * mha_apply_jacobian refuses give MHA_ERR_INVALID with Y untouched.  No allocation and no host synchronisation.      */
+#define MHA_APPLY_MAX_VECTORS 8     /* vectors one launch carries; more are taken in passes */
+int mha_apply_jacobian_multi(mha_context *ctx, int flags, const double *u_dev, const double *u_prev_dev,
+                             const double *u_stage_dev, int nvec, const double *x_dev, int64_t ldx,
+                             double *y_dev, int64_t ldy);
 /* replaces: scatterJac / scatterRes  assemblyManager.cpp:3882-3935, 3943-3978          */
 int mha_scatter_local(mha_context *ctx, const double *local_J_dev, const double *local_res_dev,
                       double *res_dev, double *crs_vals_dev);

@@ -33,10 +33,13 @@ EXPORTS = [
     "mha_kl_indices", "mha_swhdg_set_subgrids", "mha_swhdg_condensed_subgrid", "mha_swhdg_subgrid_blocks",
     "mha_mesh_swhdg_subgrids_sizes", "mha_mesh_swhdg_subgrids",
     "mha_num_derived", "mha_derived_name", "mha_get_derived_values", "mha_apply_jacobian",
+    "mha_jacobian_diagonal", "mha_apply_jacobian_multi",
 ]
 KL_MAX_TERMS = 8  # MHA_KL_MAX_TERMS: KL roots per direction the kernels evaluate
 MASS_ON_THE_FLY, MASS_LOCAL, MASS_DATABASE, MASS_DATABASE_SPARSE = 0, 1, 2, 3
 ASSEMBLE_OVERWRITE, APPLY_TRANSPOSE = 2, 32  # the flags of mha_apply_jacobian
+APPLY_MAX_VECTORS = 8  # MHA_APPLY_MAX_VECTORS: vectors one launch of mha_apply_jacobian_multi carries
+ERR_INVALID = 1  # MHA_ERR_INVALID
 SWH_INTERFACE, SWH_FARFIELD, SWH_SLIP = 0, 1, 2
 BASIS_HGRAD, BASIS_HVOL, BASIS_HDIV = 0, 1, 2
 PHYSICS_IDS = {"thermal": 1, "porousMixed": 2, "navierstokes": 3, "shallowwaterHybridized": 4,
@@ -132,6 +135,9 @@ def load_library():
         _lib.mha_database_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.mha_apply_mass_matrix_free.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         _lib.mha_apply_jacobian.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        _lib.mha_jacobian_diagonal.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        _lib.mha_apply_jacobian_multi.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [
+            C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
         _lib.mha_num_boundary_groups.argtypes = [C.c_void_p]
         _lib.mha_assemble_boundary.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         _lib.mha_boundary_update.argtypes = [C.c_void_p, C.c_int]
@@ -858,6 +864,29 @@ class Block:
         time-integration seeding, fixed rows zero -- never formed (mha_apply_jacobian)."""
         flags = (ASSEMBLE_OVERWRITE if overwrite else 0) | (APPLY_TRANSPOSE if transpose else 0)
         _check(load_library().mha_apply_jacobian(self._h, flags, _ptr(u), _ptr(u_prev), _ptr(u_stage), _ptr(x), _ptr(y)))
+
+    def jacobian_diagonal(self, u, d, overwrite=False, u_prev=None, u_stage=None):
+        """d += diag(A) (overwrite: d = ...) with the matrix of apply_jacobian, never formed (mha_jacobian_diagonal).  d is
+        zero where A is: on fixed rows and on rows the module leaves empty."""
+        _check(load_library().mha_jacobian_diagonal(self._h, ASSEMBLE_OVERWRITE if overwrite else 0, _ptr(u), _ptr(u_prev),
+                                                    _ptr(u_stage), _ptr(d)))
+
+    def apply_jacobian_multi(self, u, X, Y, transpose=False, overwrite=False, u_prev=None, u_stage=None):
+        """Y[k] += A X[k] (transpose: A^T X[k]; overwrite: Y[k] = ...) for every row k of X (mha_apply_jacobian_multi).
+        X, Y: 2-D float64 device tensors [K, >= nrows] with stride(1) == 1 and the same shape -- a Krylov basis; the
+        leading dimension is stride(0), and columns past nrows are never written."""
+        import torch
+        for name, t in (("X", X), ("Y", Y)):
+            if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() != 2 or t.dtype != torch.float64
+                    or (t.shape[1] > 1 and t.stride(1) != 1)):
+                raise MhaError(ERR_INVALID, "apply_jacobian_multi: %s must be a 2-D float64 device tensor, contiguous in "
+                               "its last dimension" % name)
+        if X.shape != Y.shape:
+            raise MhaError(ERR_INVALID, "apply_jacobian_multi: X %s and Y %s differ in shape" % (tuple(X.shape), tuple(Y.shape)))
+        ld = lambda t: t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+        flags = (ASSEMBLE_OVERWRITE if overwrite else 0) | (APPLY_TRANSPOSE if transpose else 0)
+        _check(load_library().mha_apply_jacobian_multi(self._h, flags, _ptr(u), _ptr(u_prev), _ptr(u_stage), X.shape[0],
+                                                       C.c_void_p(X.data_ptr()), ld(X), C.c_void_p(Y.data_ptr()), ld(Y)))
 
     def swhdg_condensed_element(self, u, lam, schur=None, gvec=None, du=None, num_singular=None, side_types=None,
                                 farfield=None, u_prev=None, u_stage=None):

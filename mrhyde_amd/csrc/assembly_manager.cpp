@@ -934,6 +934,65 @@ void AssemblyManager::applyJacobian(int flags, const double *u, const double *u_
   timedEnd();
 }
 
+// The diagonal and the multi-vector products take applyJacobian's route: the same checks, the state bound, the request in
+// wkset_.apply, the module's volume terms under a guard that resets the request.
+namespace {
+struct ApplyRestore {  // a refusal inside the module leaves the workset as an assembly expects it
+  Workset &w;
+  ~ApplyRestore() {
+    w.apply.mode = 0;
+    w.apply.nvec = 0;
+    w.use_point_engine = false;
+  }
+};
+}  // namespace
+
+// d (+)= diag(A), A the matrix of applyJacobian: mode 3 of the workset's request (kernels/jacobian_diagonal.hip).
+void AssemblyManager::jacobianDiagonal(int flags, const double *u, const double *u_prev, const double *u_stage, double *d) {
+  MHA_REQUIRE((flags & ~MHA_ASSEMBLE_OVERWRITE) == 0, MHA_ERR_INVALID,
+              "mha_jacobian_diagonal takes MHA_ASSEMBLE_OVERWRITE only (flags " << flags << ")");
+  MHA_REQUIRE(has_mesh_, MHA_ERR_INVALID, "no mesh: call mha_set_mesh first");
+  MHA_REQUIRE(physics_ != nullptr, MHA_ERR_INVALID, "no physics module: call mha_physics_select first");
+  MHA_REQUIRE(has_graph_, MHA_ERR_INVALID, "no CRS graph: call mha_set_graph first");
+  MHA_REQUIRE(d, MHA_ERR_INVALID, "null vector");
+  bindState(u, u_prev, u_stage);
+  wkset_.apply.mode = 3;
+  wkset_.apply.overwrite = (flags & MHA_ASSEMBLE_OVERWRITE) ? 1 : 0;
+  wkset_.apply.x = nullptr;
+  wkset_.apply.y = d;
+  wkset_.apply.nvec = 0;
+  ApplyRestore restore{wkset_};
+  timedBegin();
+  launchPointEngine(0, ElemOut(), 0, nelem_);
+  timedEnd();
+}
+
+// Y_k (+)= A X_k / A^T X_k for nvec vectors at x + k ldx, y + k ldy (kernels/jacobian_apply_multi.hip).
+void AssemblyManager::applyJacobianMulti(int flags, const double *u, const double *u_prev, const double *u_stage, int nvec,
+                                         const double *x, int64_t ldx, double *y, int64_t ldy) {
+  MHA_REQUIRE((flags & ~(MHA_ASSEMBLE_OVERWRITE | MHA_APPLY_TRANSPOSE)) == 0, MHA_ERR_INVALID,
+              "mha_apply_jacobian_multi takes MHA_ASSEMBLE_OVERWRITE and MHA_APPLY_TRANSPOSE only (flags " << flags << ")");
+  MHA_REQUIRE(has_mesh_, MHA_ERR_INVALID, "no mesh: call mha_set_mesh first");
+  MHA_REQUIRE(physics_ != nullptr, MHA_ERR_INVALID, "no physics module: call mha_physics_select first");
+  MHA_REQUIRE(has_graph_, MHA_ERR_INVALID, "no CRS graph: call mha_set_graph first");
+  MHA_REQUIRE(x && y, MHA_ERR_INVALID, "null vector");
+  MHA_REQUIRE(nvec >= 1, MHA_ERR_INVALID, "nvec = " << nvec << ": at least one vector");
+  MHA_REQUIRE(ldx >= nrows_ && ldy >= nrows_, MHA_ERR_INVALID,
+              "ldx = " << ldx << ", ldy = " << ldy << ": a vector holds nrows = " << nrows_ << " entries");
+  bindState(u, u_prev, u_stage);
+  wkset_.apply.mode = (flags & MHA_APPLY_TRANSPOSE) ? 2 : 1;
+  wkset_.apply.overwrite = (flags & MHA_ASSEMBLE_OVERWRITE) ? 1 : 0;
+  wkset_.apply.x = x;
+  wkset_.apply.y = y;
+  wkset_.apply.nvec = nvec;
+  wkset_.apply.ldx = ldx;
+  wkset_.apply.ldy = ldy;
+  ApplyRestore restore{wkset_};
+  timedBegin();
+  launchPointEngine(0, ElemOut(), 0, nelem_);
+  timedEnd();
+}
+
 // reference: AssemblyManager::getMass / getWeightedMass (assemblyManager.cpp:7776-7925): dense element mass matrices,
 // accumulated (+=) into local_mass[E][n][n] in LID-position order.  Runs the point engine with the value slots as
 // the "flux" (kernels/point_engine.hip, mass mode): the mass matrix is the B^T C B product with C = weights.
@@ -2308,6 +2367,9 @@ int64_t AssemblyManager::info(const std::string &key) const {
   if (key == "last_path") return last_path_;
   if (key == "jacobian_apply_lds_bytes") return static_cast<int64_t>(wkset_.apply.lds_bytes);  // last mha_apply_jacobian: LDS per workgroup
   if (key == "jacobian_apply_waves") return wkset_.apply.waves;  // and its wavefronts (= elements) per workgroup
+  if (key == "jacobian_apply_vectors") return wkset_.apply.vectors;  // last mha_apply_jacobian_multi: vectors per launch (Kc)
+  if (key == "jacobian_diag_lds_bytes") return static_cast<int64_t>(wkset_.apply.diag_lds_bytes);  // last mha_jacobian_diagonal
+  if (key == "jacobian_diag_waves") return wkset_.apply.diag_waves;
   if (key == "jacobian_database_mode") return last_db_mode_;  // the last affine row-owner Jacobian replicated one block per pattern
   if (key == "block_pattern_rep_launches") return rep_launches_;  // representative launches of the geometry-database mode so far
   if (key == "affine_shapes") return ro_.ready ? ro_.k1_plan.num_shapes : 0;  // distinct geometry records behind the residual kernel's database index

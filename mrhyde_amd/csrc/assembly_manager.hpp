@@ -56,6 +56,11 @@ class AssemblyManager {
   // y (+)= A x or A^T x with the matrix assembleJacRes stores (volume terms, fixed rows zero), never formed
   // (kernels/jacobian_apply.hip); flags: MHA_ASSEMBLE_OVERWRITE, MHA_APPLY_TRANSPOSE
   void applyJacobian(int flags, const double *u, const double *u_prev, const double *u_stage, const double *x, double *y);
+  // d (+)= diag(A) (kernels/jacobian_diagonal.hip; flags: MHA_ASSEMBLE_OVERWRITE) and the products for nvec vectors
+  // x + k ldx -> y + k ldy (kernels/jacobian_apply_multi.hip), on the same route
+  void jacobianDiagonal(int flags, const double *u, const double *u_prev, const double *u_stage, double *d);
+  void applyJacobianMulti(int flags, const double *u, const double *u_prev, const double *u_stage, int nvec,
+                          const double *x, int64_t ldx, double *y, int64_t ldy);
   void swhdgElementBlocks(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
                           const uint8_t *side_types, const double *farfield, double *res, double *blocks);
   // SubGridDtN_Solver::nonlinearSolver for HDG elements with element-local interior unknowns (subgridDtN_solver.cpp:909-1041)

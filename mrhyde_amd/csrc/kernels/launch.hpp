@@ -197,4 +197,17 @@ void launch_jacobian_apply(const BlockDev &b, const VarLayoutDev &vl, const Phys
                            const double *x, double *y, int transpose, int overwrite, hipStream_t stream,
                            size_t *lds_bytes = nullptr, int *waves = nullptr);
 
+// jacobian_diagonal.hip: d += diag(A) with the same A; overwrite, lds_bytes and waves as above
+void launch_jacobian_diagonal(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp, const TimeDev &tm,
+                              double *d, int overwrite, hipStream_t stream, size_t *lds_bytes = nullptr,
+                              int *waves = nullptr);
+
+// jacobian_apply_multi.hip: the products for nvec >= 1 vectors, vector k at x + k ldx / y + k ldy (ldx, ldy >= b.nrows), in
+// passes of Kc <= MHA_APPLY_MAX_VECTORS vectors per launch, Kc chosen per shape.  overwrite zeroes y + k ldy + [0, b.nrows)
+// only.  lds_bytes / waves / vectors (may be null): LDS per workgroup, wavefronts per workgroup and Kc of the first pass
+void launch_jacobian_apply_multi(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp, const TimeDev &tm,
+                                 int nvec, const double *x, int64_t ldx, double *y, int64_t ldy, int transpose,
+                                 int overwrite, hipStream_t stream, size_t *lds_bytes = nullptr, int *waves = nullptr,
+                                 int *vectors = nullptr);
+
 }  // namespace mha

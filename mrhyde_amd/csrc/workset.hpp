@@ -53,14 +53,18 @@ class Workset {
   // multi-variable point engine (kernels/point_engine.hip): variable/slot layout, orientation signs
   VarLayoutDev layout;
   bool use_point_engine = false;
-  // matrix-free Jacobian product (kernels/jacobian_apply.hip): mode != 0 sends the module's volume terms to it instead
-  // of the element assembly (1: y (+)= A x, 2: y (+)= A^T x); lds_bytes / waves report the launch
+  // matrix-free Jacobian requests: mode != 0 sends the module's volume terms to them instead of the element assembly.
+  // 1: y (+)= A x, 2: y (+)= A^T x (kernels/jacobian_apply.hip; with nvec >= 1 the vectors x + k ldx -> y + k ldy,
+  // kernels/jacobian_apply_multi.hip), 3: y (+)= diag(A) (kernels/jacobian_diagonal.hip).  lds_bytes / waves / vectors
+  // report the last product's launch, diag_* the last diagonal's
   struct Apply {
     int mode = 0, overwrite = 0;
     const double *x = nullptr;
     double *y = nullptr;
-    size_t lds_bytes = 0;
-    int waves = 0;
+    int nvec = 0;  // 0: the single product
+    int64_t ldx = 0, ldy = 0;
+    size_t lds_bytes = 0, diag_lds_bytes = 0;
+    int waves = 0, vectors = 0, diag_waves = 0;
   } apply;
   bool single_hgrad = true;  // basis / basis_grad views exist for single-variable HGRAD blocks only
   hipStream_t stream = nullptr;
@@ -94,9 +98,17 @@ class Workset {
 };
 
 // A module's volume terms on its point function: the element assembly into w.res (kernels/point_engine.hip) or, when the
-// workset carries a product request, y (+)= A x / A^T x with the same Jacobian (kernels/jacobian_apply.hip).
+// workset carries a request, y (+)= A x / A^T x for one vector or several, or diag(A), with the same Jacobian
+// (kernels/jacobian_apply.hip, jacobian_apply_multi.hip, jacobian_diagonal.hip).
 inline void launch_volume_points(Workset &w, const BlockDev &b, const PhysParamsDev &pp) {
-  if (w.apply.mode) {
+  if (w.apply.mode == 3) {
+    launch_jacobian_diagonal(b, w.layout, pp, w.time_dev, w.apply.y, w.apply.overwrite, w.stream, &w.apply.diag_lds_bytes,
+                             &w.apply.diag_waves);
+  } else if (w.apply.mode && w.apply.nvec) {
+    launch_jacobian_apply_multi(b, w.layout, pp, w.time_dev, w.apply.nvec, w.apply.x, w.apply.ldx, w.apply.y, w.apply.ldy,
+                                w.apply.mode == 2, w.apply.overwrite, w.stream, &w.apply.lds_bytes, &w.apply.waves,
+                                &w.apply.vectors);
+  } else if (w.apply.mode) {
     launch_jacobian_apply(b, w.layout, pp, w.time_dev, w.apply.x, w.apply.y, w.apply.mode == 2, w.apply.overwrite,
                           w.stream, &w.apply.lds_bytes, &w.apply.waves);
   } else {
