@@ -198,7 +198,9 @@ int mha_set_function(mha_context *ctx, const char *name, int kind, double amp, c
  * replaces: FunctionManager::addFunction + decomposeFunctions + evaluate for position/time expressions
  *   src/managers/functionManager.cpp:60-93, 95-540, 543-860, src/tools/interpreter.cpp.
  * Grammar: numbers; x y z t nx ny nz h pi (functionManager.cpp:21); + - * / ^, unary minus, < > <= >=, parentheses;
- * sin cos tan exp log abs sqrt sinh cosh (:22).  Solution fields, other named functions and the view reductions
+ * sin cos tan exp log abs sqrt sinh cosh (:22).  nx ny nz are the unit normal in side functions (Neumann / Dirichlet /
+ * flux data) and 0 in volume functions; h is 0 wherever no caller supplies it -- today everywhere, as in the reference,
+ * which gives the h leaf no data (:386-404).  Solution fields, other named functions and the view reductions
  * max/min/mean/emax/emin/emean are rejected (MHA_ERR_INVALID).  `t` is the time given to mha_set_time.              */
 int mha_set_function_expression(mha_context *ctx, const char *name, const char *expression);
 /* syntax / vocabulary check of a deck string without a context (host only, no GPU needed): MHA_OK or MHA_ERR_INVALID */

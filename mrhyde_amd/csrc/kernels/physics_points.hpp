@@ -27,10 +27,11 @@ struct PointArgs {
 };
 
 // a function of the module at the point as a Dual: field-dependent deck strings carry the derivative with respect to the
-// direction the point's fields are seeded with, everything else is a constant of that direction
+// direction the point's fields are seeded with, everything else is a constant of that direction.  nx ny nz h are 0 as
+// in eval_func's volume callers (a.h is the stabilisation's element size, not an operand of deck strings)
 template <int DIM>
 __device__ __forceinline__ Dual func_dual(const FuncDesc &f, const PointArgs<DIM> &a) {
-  if (f.kind == MHA_FUNC_EXPRESSION) return eval_expression_dual<DIM>(f, a.x, nullptr, a.h, a.U, a.Ud);
+  if (f.kind == MHA_FUNC_EXPRESSION) return eval_expression_dual<DIM>(f, a.x, nullptr, 0.0, a.U, a.Ud);
   return mk(eval_func<DIM, false>(f, a.e, a.q, a.nq, a.x));
 }
 

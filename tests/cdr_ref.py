@@ -54,6 +54,10 @@ def field_dict(oracle, F, names, time=0.0):
     for d, c in enumerate("xyz"[:dim]):
         fields[c] = oracle.ADView(F["ip"][..., d], W=n)
     fields["t"] = oracle.ADView(np.full(F["wts"].shape, float(time)), W=n)
+    # the known variables without data in a volume function: z on a 2-D block, the normal, and h, whose leaf the
+    # reference never fills (functionManager.cpp:386-404)
+    for c in ["z"][:3 - dim] + ["nx", "ny", "nz", "h"]:
+        fields[c] = oracle.ADView(np.zeros(F["wts"].shape), W=n)
     return fields
 
 

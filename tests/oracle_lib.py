@@ -965,7 +965,7 @@ def deck_eval_ad(text, fields, functions=None, _open=()):
 
 
 def assemble_thermal_fields(dim, order, qdeg, nodes, lids, offsets, u, funcs, *, fixed=None, rowptr=None, colind=None,
-                            functions=None):
+                            functions=None, time=0.0):
     """thermal::volumeResidual (src/physics/thermal.cpp:71-165, steady) with its functions given as deck strings that may
     read the solution fields, AD arrays of width n seeded at off(j) (workset.cpp:823-859), then the scatter of
     assemblyManager.cpp:4031-4145 (-res.val(), +res.dx(col), fixed rows skipped).  funcs: 'thermal source',
@@ -987,7 +987,9 @@ def assemble_thermal_fields(dim, order, qdeg, nodes, lids, offsets, u, funcs, *,
         gd[:, :, off] = np.transpose(G[..., d], (0, 2, 1))
         fields["grad(e)[%s]" % c] = ADView(np.einsum("ej,ejq->eq", ue, G[..., d]), gd)
         fields[c] = ADView(ip[..., d], W=n)
-    fields["t"] = ADView(np.zeros((E, nq)), W=n)
+    fields["t"] = ADView(np.full((E, nq), float(time)), W=n)
+    for c in ["z"][:3 - dim] + ["nx", "ny", "nz", "h"]:  # known variables without data in a volume function
+        fields[c] = ADView(np.zeros((E, nq)), W=n)
 
     def fn(name, default):
         v = funcs.get(name, default)
