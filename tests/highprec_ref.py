@@ -1,0 +1,645 @@
+"""The extended-precision yardstick of the HGRAD modules (thermal, navierstokes, linearelasticity): element arrays,
+global CRS values and residuals in numpy's 80-bit longdouble / clongdouble (eps 1.08e-19) from 1-D ingredients that mpmath
+computes at 40 digits, and beside every entry the SCALE of its own sum, so that an entry is judged by its own condition.
+
+TEST INFRASTRUCTURE (the checker), imported by tests/test_highprec.py and tests/test_highprec_gpu.py only.  It shares no
+code, tables or derivative rules with oracle/ or mrhyde_amd/: quadrature and Lagrange tables come from mpmath, the
+geometry from the multilinear map of the element's vertices, the modules are restated as point functions from the
+reference's loop nests, and their derivatives are complex steps (no hand-written derivative, no AD rules).
+
+  res_i = -sum_q T(i,q) . F(q) w(q)                            S_res_i = sum_q sum_k |T_k(i,q)| |F_k(q)| w(q)
+  J_ij  =  sum_q T(i,q)^T [alpha_u dF/dU + alpha_t dF/dUdot] T(j,q) w(q)
+                                                               S_J_ij  = sum_q sum_kl |T_k(i,q)| |C_kl(q)| |T_l(j,q)| w(q)
+  y = A x:  S_y_i = sum_j S_J_ij |x_j|
+
+with T the slot values of a basis function at a point (value and gradient components of its variable, zero elsewhere),
+F the module's point function and C its derivative.  The criterion (distance): d = |got - yardstick| / (2^-53 S), and
+got == 0.0 exactly where S == 0.
+
+Reference lines restated here:
+  * thermal::volumeResidual                  src/physics/thermal.cpp:125-163
+  * navierstokes::volumeResidual, computeTau src/physics/navierstokes.cpp:82-849, :1054-1079 (uz through uy's offsets: :688)
+  * linearelasticity::volumeResidual, computeStress  src/physics/linearelasticity.cpp:92-238, :985-1073
+  * Workset::computeSolnTransientSeeded      src/tools/workset.cpp:589-623
+  * Workset::getElementSize                  src/tools/workset.cpp:2666-2679
+  * the scatter (-res.val(), +res.dx(col), fixed rows skipped)  src/managers/assemblyManager.cpp:4031-4145
+"""
+import functools
+
+import mpmath
+import numpy as np
+
+LD, CLD = np.longdouble, np.clongdouble
+EPS64 = 2.0 ** -53
+H_STEP = LD("1e-30")
+_DPS = 40
+
+
+# ---- measured constants -----------------------------------------------------------------------------------------------
+# K_oracle[(module, family)]: the CPU oracle's largest distance d from this yardstick over every entry (element arrays,
+# CRS values, residual) of every shape of the family, steady and transient, as tests/test_highprec.py measures and prints
+# it (the measurement stands beside each constant; the table is in profiles/extended_precision_yardstick.md).
+#   * thermal and navierstokes (the C oracle: plain loops, -ffp-contract=off, the same figure on every run): the next
+#     integer that is at least one half above the measurement (above 1000: the next multiple of ten);
+#   * linearelasticity and thermal's nonlinear diffusion (Python restatements on numpy's einsum, whose summation order
+#     follows the vector units of the CPU it runs on): the measurement times 1.25, rounded up to two digits.
+# The CPU test fails when the oracle exceeds its constant or falls below two thirds of it.  The device's bound is
+# max(8 K_oracle, 8).
+K_ORACLE = {
+    ("thermal",          "unit"):              23,      # measured 22.10
+    ("thermal",          "stretched aligned"): 23,      # measured 21.74
+    ("thermal",          "stretched sheared"): 1120,    # measured 1119
+    ("thermal",          "stretched warped"):  28,      # measured 26.94
+    ("thermal",          "units small"):       22,      # measured 21.13
+    ("thermal",          "units large"):       23,      # measured 21.99
+    ("thermal",          "unit advection"):    23,      # measured 22.31
+    ("thermal",          "unit nonlinear"):    25,      # measured 19.82 (Python restatement)
+    ("navierstokes",     "unit"):              23,      # measured 22.23
+    ("navierstokes",     "stretched aligned"): 45,      # measured 43.90
+    ("navierstokes",     "stretched sheared"): 1020,    # measured 1018
+    ("navierstokes",     "stretched warped"):  69,      # measured 67.98
+    ("navierstokes",     "units small"):       41,      # measured 40.41
+    ("navierstokes",     "units large"):       26,      # measured 24.96
+    ("navierstokes",     "rest"):              63,      # measured 62.36
+    ("linearelasticity", "unit"):              23,      # measured 18.28
+    ("linearelasticity", "stretched aligned"): 25,      # measured 19.83
+    ("linearelasticity", "stretched sheared"): 1300,    # measured 1029
+    ("linearelasticity", "stretched warped"):  26,      # measured 20.08
+    ("linearelasticity", "units small"):       25,      # measured 19.28
+    ("linearelasticity", "units large"):       23,      # measured 18.38
+    ("linearelasticity", "unit plane stress"): 23,      # measured 18.28
+}
+
+
+def device_bound(module, family):
+    return max(8.0 * K_ORACLE[(module, family)], 8.0)
+
+
+# ---- 1-D ingredients: mpmath at 40 digits, rounded once ---------------------------------------------------------------
+def _ld(x):
+    return LD(mpmath.nstr(x, 30, strip_zeros=False))
+
+
+@functools.lru_cache(maxsize=None)
+def gauss_mp(n):
+    """Gauss-Legendre points and weights on [-1, 1] as mpf: the roots of P_n, w = 2 / ((1 - x^2) P_n'(x)^2)."""
+    with mpmath.workdps(max(_DPS, mpmath.mp.dps)):
+        P = lambda x: mpmath.legendre(n, x)
+        xs = [mpmath.findroot(P, mpmath.cos(mpmath.pi * (4 * k + 3) / (4 * n + 2))) for k in range(n)]
+        xs = sorted(xs)
+        for a, b in zip(xs, xs[1:]):
+            assert b - a > mpmath.mpf(10) ** -10, "a root found twice"
+        ws = []
+        for x in xs:
+            dP = n * (x * mpmath.legendre(n, x) - mpmath.legendre(n - 1, x)) / (x * x - 1)
+            ws.append(2 / ((1 - x * x) * dP * dP))
+        return tuple(xs), tuple(ws)
+
+
+def gauss_npts(degree):
+    return degree // 2 + 1
+
+
+def lagrange_mp(order, x):
+    """Values and derivatives at x (mpf) of the Lagrange polynomials on the order + 1 equispaced nodes of [-1, 1]."""
+    with mpmath.workdps(max(_DPS, mpmath.mp.dps)):
+        nd = [mpmath.mpf(-1) + mpmath.mpf(2 * k) / order for k in range(order + 1)]
+        val, der = [], []
+        for k in range(order + 1):
+            v = mpmath.mpf(1)
+            for m in range(order + 1):
+                if m != k:
+                    v *= (x - nd[m]) / (nd[k] - nd[m])
+            d = mpmath.mpf(0)
+            for l in range(order + 1):
+                if l == k:
+                    continue
+                t = 1 / (nd[k] - nd[l])
+                for m in range(order + 1):
+                    if m != k and m != l:
+                        t *= (x - nd[m]) / (nd[k] - nd[m])
+                d += t
+            val.append(v)
+            der.append(d)
+        return val, der
+
+
+@functools.lru_cache(maxsize=None)
+def line_tables(order, npts):
+    """(points [q], weights [q], values [order + 1][q], derivatives [order + 1][q]) as longdouble."""
+    xs, ws = gauss_mp(npts)
+    V, D = np.zeros((order + 1, npts), LD), np.zeros((order + 1, npts), LD)
+    for q, x in enumerate(xs):
+        v, d = lagrange_mp(order, x)
+        for k in range(order + 1):
+            V[k, q], D[k, q] = _ld(v[k]), _ld(d[k])
+    return np.array([_ld(x) for x in xs]), np.array([_ld(w) for w in ws]), V, D
+
+
+@functools.lru_cache(maxsize=None)
+def node_tables(order, at_order):
+    """Lagrange values of `order` at the equispaced nodes of `at_order`: [order + 1][at_order + 1] (longdouble)."""
+    with mpmath.workdps(max(_DPS, mpmath.mp.dps)):
+        V = np.zeros((order + 1, at_order + 1), LD)
+        for j in range(at_order + 1):
+            v, _ = lagrange_mp(order, mpmath.mpf(-1) + mpmath.mpf(2 * j) / at_order)
+            for k in range(order + 1):
+                V[k, j] = _ld(v[k])
+        return V
+
+
+# ---- tensor products ----------------------------------------------------------------------------------------------------
+def _tensor(dim, V, D):
+    """Tensor product of 1-D tables V, D [f][q]: B [f^dim][q^dim], G [..][..][dim]; the x index runs fastest."""
+    if dim == 2:
+        B = np.einsum("bj,ai->baji", V, V)
+        G = np.stack([np.einsum("bj,ai->baji", V, D), np.einsum("bj,ai->baji", D, V)], axis=-1)
+    else:
+        B = np.einsum("ck,bj,ai->cbakji", V, V, V)
+        G = np.stack([np.einsum("ck,bj,ai->cbakji", V, V, D), np.einsum("ck,bj,ai->cbakji", V, D, V),
+                      np.einsum("ck,bj,ai->cbakji", D, V, V)], axis=-1)
+    nf, nq = V.shape[0] ** dim, V.shape[1] ** dim
+    return B.reshape(nf, nq), G.reshape(nf, nq, dim)
+
+
+def _vertex_perm(dim):
+    """Tensor index (x fastest) of the vertices in the cell's vertex order: counter-clockwise bottom, then top."""
+    sg = [(0, 0), (1, 0), (1, 1), (0, 1)]
+    if dim == 2:
+        return [a + 2 * b for a, b in sg]
+    return [a + 2 * b + 4 * c for c in (0, 1) for a, b in sg]
+
+
+def ref_tables(dim, order, qdeg):
+    """Reference-cell tables: B [f][q], G [f][q][dim] of the order-`order` basis, NV / NG of the multilinear vertex
+    functions (cell vertex order), w [q]."""
+    npts = gauss_npts(qdeg)
+    _, w1, V, D = line_tables(order, npts)
+    _, _, V1, D1 = line_tables(1, npts)
+    B, G = _tensor(dim, V, D)
+    NV, NG = _tensor(dim, V1, D1)
+    perm = _vertex_perm(dim)
+    w = w1
+    for _ in range(dim - 1):
+        w = np.multiply.outer(w1, w).reshape(-1)
+    return dict(B=B, G=G, NV=NV[perm], NG=NG[perm], w=w)
+
+
+# ---- geometry -----------------------------------------------------------------------------------------------------------
+def cofactor_inverse(J):
+    """det [..] and inverse [..][d][d] of J [..][d][d] by cofactors (numpy.linalg has no longdouble)."""
+    d = J.shape[-1]
+    if d == 2:
+        det = J[..., 0, 0] * J[..., 1, 1] - J[..., 0, 1] * J[..., 1, 0]
+        adj = np.stack([np.stack([J[..., 1, 1], -J[..., 0, 1]], -1), np.stack([-J[..., 1, 0], J[..., 0, 0]], -1)], -2)
+    else:
+        c = lambda i, j, k, l: J[..., i, j] * J[..., k, l] - J[..., i, l] * J[..., k, j]
+        adj = np.stack([np.stack([c(1, 1, 2, 2), -c(0, 1, 2, 2), c(0, 1, 1, 2)], -1),
+                        np.stack([-c(1, 0, 2, 2), c(0, 0, 2, 2), -c(0, 0, 1, 2)], -1),
+                        np.stack([c(1, 0, 2, 1), -c(0, 0, 2, 1), c(0, 0, 1, 1)], -1)], -2)
+        det = J[..., 0, 0] * adj[..., 0, 0] + J[..., 0, 1] * adj[..., 1, 0] + J[..., 0, 2] * adj[..., 2, 0]
+    return det, adj / det[..., None, None]
+
+
+def geometry(nodes, rt):
+    """x [E][q][dim], Jinv [E][q][dim][dim], wts [E][q] of the multilinear map of nodes [E][2^dim][dim]."""
+    X = np.asarray(nodes).astype(LD)
+    x = np.einsum("evi,vq->eqi", X, rt["NV"])
+    J = np.einsum("evi,vqj->eqij", X, rt["NG"])        # J_ij = d x_i / d xi_j
+    det, Jinv = cofactor_inverse(J)
+    assert np.all(det > 0)
+    return x, Jinv, rt["w"][None, :] * det
+
+
+# ---- the block: slot tables T, seeding ----------------------------------------------------------------------------------
+class Block:
+    """m: a mesh dict of tests/oracle_lib.py's layout (nodes, lids, offsets, ndof and, for several variables, orders and
+    varptr; a single-variable mesh gives `order`).  Slots: variable v -> [value, d/dx, d/dy(, d/dz)] at v (1 + dim)."""
+
+    def __init__(self, m, qdeg, order=None, test_var=None):
+        self.nodes = np.asarray(m["nodes"], dtype=np.float64)
+        self.lids = np.asarray(m["lids"])
+        self.E, self.n = self.lids.shape
+        self.dim = dim = self.nodes.shape[2]
+        self.ndof = int(m["ndof"])
+        off = np.asarray(m["offsets"])
+        if order is not None:
+            self.orders, self.offs = [int(order)], [off]
+        else:
+            self.orders = [int(o) for o in m["orders"]]
+            self.offs = [off[m["varptr"][v]:m["varptr"][v + 1]] for v in range(len(self.orders))]
+        self.nv, self.S = len(self.orders), 1 + dim
+        K = self.nv * self.S
+        rt0 = ref_tables(dim, 1, qdeg)
+        self.x, Jinv, self.w = geometry(self.nodes, rt0)
+        self.nq = self.w.shape[1]
+        self.h = (self.w.sum(axis=1) ** (LD(1) / dim))[:, None]        # getElementSize
+        T = np.zeros((self.E, self.n, self.nq, K), LD)
+        for v, (o, of) in enumerate(zip(self.orders, self.offs)):
+            rt = ref_tables(dim, o, qdeg)
+            assert len(of) == rt["B"].shape[0]
+            T[:, of, :, v * self.S:v * self.S + 1] = rt["B"][None, :, :, None]
+            T[:, of, :, v * self.S + 1:(v + 1) * self.S] = np.einsum("eqji,fqj->efqi", Jinv, rt["G"])   # J^-T grad
+        self.T = T
+        # rows: test_var[v] = the variable through whose offsets the rows of v's equation are scattered
+        self.Ttest = T
+        if test_var is not None and list(test_var) != list(range(self.nv)):
+            self.Ttest = np.zeros_like(T)
+            for v, tv in enumerate(test_var):
+                assert self.orders[v] == self.orders[tv]
+                self.Ttest[:, self.offs[tv], :, v * self.S:(v + 1) * self.S] += T[:, self.offs[v], :, v * self.S:(v + 1) * self.S]
+
+    # -- its own check of the dof ordering -------------------------------------------------------------------------------
+    def check_ordering(self):
+        """(1) every global row sits at one physical point in all elements that share it; (2) the nodal field a . x(node)
+        comes out of the tables as a . x(q) with gradient a.  Returns the node coordinates [ndof][dim]."""
+        dim = self.dim
+        X = self.nodes.astype(LD)
+        size = (X.max(axis=1) - X.min(axis=1)).max(axis=1)                         # [E]
+        xn = np.full((self.ndof, dim), np.nan, LD)
+        perm = _vertex_perm(dim)
+        for v, (o, of) in enumerate(zip(self.orders, self.offs)):
+            V1 = node_tables(1, o)
+            NVn, _ = _tensor(dim, V1, np.zeros_like(V1))
+            pts = np.einsum("evi,vf->efi", X, NVn[perm])                          # node of basis function f
+            rows = self.lids[:, of]
+            for e in range(self.E):
+                for f in range(len(of)):
+                    r = rows[e, f]
+                    if np.isnan(xn[r, 0]):
+                        xn[r] = pts[e, f]
+                    assert np.abs(xn[r] - pts[e, f]).max() <= 1e-12 * size[e], ("row placed at two points", v, e, f)
+        assert not np.isnan(xn).any(), "a row that no element reaches"
+        a = np.array([0.7, -1.3, 0.45], LD)[:dim]
+        U = self.fields((xn * a).sum(axis=1)[self.lids])
+        tol = 1e-15 * max(float(np.abs(xn).max()), float(size.max()))
+        for v in range(self.nv):
+            assert np.abs(U[v * self.S] - (self.x * a).sum(axis=2)).max() <= tol, ("a . x(node) != a . x(q)", v)
+            for d in range(dim):
+                assert np.abs(U[v * self.S + 1 + d] - a[d]).max() <= 1e-15 * float(size.max() / size.min() * 1e3), v
+        return xn
+
+    # -- fields and seeding ----------------------------------------------------------------------------------------------
+    def fields(self, ue):
+        """ue [E][n] (LID-position order) -> slot values [K][E][q]."""
+        return np.einsum("epqk,ep->keq", self.T, ue)
+
+    def seeded(self, u, tr):
+        """Stage value and time derivative of every row, and (alpha_u, alpha_t): workset.cpp:589-623."""
+        cu = np.asarray(u).astype(LD)
+        if tr is None:
+            return cu, np.zeros_like(cu), LD(1), LD(0)
+        A, b, bdf = (np.asarray(tr[k]).astype(LD) for k in ("butcher_A", "butcher_b", "bdf"))
+        st, dt = tr["stage"], LD(tr["dt"])
+        up, us = np.asarray(tr["u_prev"]).astype(LD), np.asarray(tr["u_stage"]).astype(LD)
+        alpha_u = A[st, st] / b[st]
+        timewt = LD(1) / dt / b[st]
+        alpha_t = bdf[0] * timewt
+        beta_u = (LD(1) - alpha_u) * up[:, 0]
+        for s in range(st):
+            beta_u = beta_u + A[st, s] / b[s] * (us[:, s] - up[:, 0])
+        beta_t = np.zeros_like(cu)
+        for s in range(1, len(bdf)):
+            beta_t = beta_t + bdf[s] * up[:, s - 1]
+        beta_t = beta_t * timewt
+        return alpha_u * cu + beta_u, alpha_t * cu + beta_t, alpha_u, alpha_t
+
+
+# ---- the modules as point functions F(U, Udot, x, params) ----------------------------------------------------------------
+def func_value(spec, x):
+    """A function of the deck at the points x [E][q][dim]: a number or ("sinprod", amp, freq)."""
+    if isinstance(spec, (int, float)):
+        return LD(spec)
+    assert spec[0] == "sinprod"
+    v = LD(spec[1])
+    for d in range(x.shape[2]):
+        v = v * np.sin(LD(spec[2][d]) * x[..., d])
+    return v
+
+
+def thermal_point(U, Ud, x, P):
+    """thermal.cpp:125-163.  params: source, diffusion (a number, sinprod, or a callable of e: "1+e*e"), rho, cp, and
+    adv = (bx, by[, bz]) or None ('include advection')."""
+    dim = x.shape[2]
+    kap = P["diffusion"](U[0]) if callable(P["diffusion"]) else func_value(P["diffusion"], x)
+    F = [None] * (1 + dim)
+    F[0] = LD(P["rho"]) * LD(P["cp"]) * Ud[0] - func_value(P["source"], x)
+    for d in range(dim):
+        F[1 + d] = kap * U[1 + d]
+    if P.get("adv") is not None:
+        for d in range(dim):
+            F[0] = F[0] + func_value(P["adv"][d], x) * U[1 + d]
+    return F
+
+
+def compute_tau(visc, vel, h, dt, transient):
+    """navierstokes.cpp:1054-1079; the branch nvel > 1e-12 is taken on the real part."""
+    C1, C2, C3 = LD(4), LD(2), LD(2) if transient else LD(0)
+    nvel = vel[0] * vel[0]
+    for v in vel[1:]:
+        nvel = nvel + v * v
+    nvel = np.where(np.real(nvel) > 1e-12, np.sqrt(np.where(np.real(nvel) > 1e-12, nvel, 1)), nvel)
+    tau = (C1 * visc / h / h) * (C1 * visc / h / h) + (C2 * nvel / h) * (C2 * nvel / h) + (C3 / dt) * (C3 / dt)
+    return 1 / np.sqrt(tau)
+
+
+def navierstokes_point(U, Ud, x, P):
+    """navierstokes.cpp:82-849, variables ux, pr, uy[, uz]; params: source ux / uy / uz, density, viscosity, useSUPG,
+    usePSPG, h [E][1], dt, transient.  (The uz rows go through uy's offsets unless fix_uz_offsets: Block(test_var=...).)"""
+    dim = x.shape[2]
+    S = 1 + dim
+    vn, pn = [0, 2, 3][:dim], 1
+    dens, visc = func_value(P["density"], x), func_value(P["viscosity"], x)
+    src = [func_value(P["source u" + c], x) for c in "xyz"[:dim]]
+    vel = [U[v * S] for v in vn]
+    pr = U[pn * S]
+    supg, pspg = bool(P.get("useSUPG")), bool(P.get("usePSPG"))
+    tau = compute_tau(visc, vel, P["h"], LD(P["dt"]), bool(P["transient"])) if supg or pspg else None
+    F = [None] * ((dim + 1) * S)
+    divu = 0
+    strong = []
+    for i, v in enumerate(vn):
+        b = v * S
+        conv = sum(vel[d] * U[b + 1 + d] for d in range(dim))
+        F[b] = (Ud[b] + conv - src[i]) * dens                                  # F of :520-521
+        for d in range(dim):
+            F[b + 1 + d] = visc * U[b + 1 + d] - (pr if d == i else 0)           # Fx, Fy, Fz of :514-519
+        divu = divu + U[b + 1 + i]
+        # stabres of :554 (= Sx / (tau wts / dens) of :813)
+        strong.append(dens * Ud[b] + dens * conv + U[pn * S + 1 + i] - dens * src[i])
+        if supg:
+            for d in range(dim):
+                F[b + 1 + d] = F[b + 1 + d] + tau * strong[i] * vel[d]          # :555-559
+    F[pn * S] = divu                                                            # :782-784
+    for d in range(dim):
+        F[pn * S + 1 + d] = strong[d] * tau / dens if pspg else 0 * pr          # :813-820
+    return F
+
+
+def linearelasticity_point(U, Ud, x, P):
+    """linearelasticity.cpp:92-238 with computeStress :985-1073; variables dx, dy[, dz]; params: lambda, mu, source dx /
+    dy / dz, incplanestress."""
+    dim = x.shape[2]
+    S = 1 + dim
+    lam, mu = func_value(P["lambda"], x), func_value(P["mu"], x)
+    g = lambda i, j: U[i * S + 1 + j]                                            # grad(d_i)[j]
+    F = [None] * (dim * S)
+    for i in range(dim):
+        F[i * S] = -func_value(P["source d" + "xyz"[i]], x) + 0 * U[0]
+        for j in range(dim):
+            if i != j:
+                sig = mu * (g(i, j) + g(j, i))
+            elif dim == 2 and P.get("incplanestress"):
+                sig = 4 * mu * g(i, i) + 2 * mu * g(1 - i, 1 - i)                 # :995, :998
+            else:
+                sig = (2 * mu + lam) * g(i, i) + lam * sum(g(k, k) for k in range(dim) if k != i)
+            F[i * S + 1 + j] = sig
+    return F
+
+
+POINT = {"thermal": thermal_point, "navierstokes": navierstokes_point, "linearelasticity": linearelasticity_point}
+
+
+def _stack(F, like):
+    return np.stack([np.broadcast_to(np.asarray(f, dtype=like.dtype), like.shape[1:]) for f in F])
+
+
+def point_derivative(point, U, Ud, x, P):
+    """F [K][E][q], dF/dU and dF/dUdot [K out][K in][E][q] by the complex step Im F(U + i h e_k) / h, h = 1e-30."""
+    K = U.shape[0]
+    Uc, Udc = U.astype(CLD), Ud.astype(CLD)
+    F = np.real(_stack(point(Uc, Udc, x, P), Uc)).astype(LD)
+    CU, CT = np.zeros((K, K) + U.shape[1:], LD), np.zeros((K, K) + U.shape[1:], LD)
+    S = 1 + x.shape[2]
+    for k in range(K):
+        Up = Uc.copy()
+        Up[k] += 1j * H_STEP
+        CU[:, k] = np.imag(_stack(point(Up, Udc, x, P), Uc)) / H_STEP
+        if k % S == 0:                               # only the value slots have a time derivative
+            Up = Udc.copy()
+            Up[k] += 1j * H_STEP
+            CT[:, k] = np.imag(_stack(point(Uc, Up, x, P), Uc)) / H_STEP
+    return F, CU, CT
+
+
+# ---- element arrays and their scales --------------------------------------------------------------------------------------
+def element_arrays(blk, module, P, u, tr=None):
+    """-> dict(local_res, local_J, S_res, S_J) in LID-position order [E][n], [E][n][n] (longdouble); local_res holds -R
+    and local_J +dR/du, the sign conventions of the ABI."""
+    ue, ud, alpha_u, alpha_t = blk.seeded(u, tr)
+    U, Ud = blk.fields(ue[blk.lids]), blk.fields(ud[blk.lids])
+    P = dict(P, h=blk.h, transient=tr is not None, dt=tr["dt"] if tr is not None else 1.0)
+    F, CU, CT = point_derivative(POINT[module], U, Ud, blk.x, P)
+    C = alpha_u * CU + alpha_t * CT
+    E, n, nq, K = blk.T.shape
+    Tt, Tr, w = blk.Ttest, blk.T, blk.w
+    Fw = np.transpose(F, (1, 2, 0)) * w[..., None]                       # [E][q][K]
+    Cw = np.transpose(C, (2, 3, 0, 1)) * w[..., None, None]              # [E][q][K out][K in]
+    out = {}
+    for tag, (a, f, c, b) in (("", (Tt, Fw, Cw, Tr)), ("S_", (np.abs(Tt), np.abs(Fw), np.abs(Cw), np.abs(Tr)))):
+        r = np.einsum("eiqk,eqk->ei", a, f)
+        Pm = np.einsum("eiqk,eqkl->eiql", a, c).reshape(E, n, nq * K)    # P = T C
+        Jm = np.matmul(Pm, np.transpose(b.reshape(E, n, nq * K), (0, 2, 1)))   # then P T
+        out[tag + "res"], out[tag + "J"] = r, Jm
+    return dict(local_res=-out["res"], local_J=out["J"], S_res=out["S_res"], S_J=out["S_J"])
+
+
+# ---- assembly -------------------------------------------------------------------------------------------------------------
+def build_graph(ndof, lids):
+    """CRS graph of the element connectivity: every row's columns ascending."""
+    cols = [set() for _ in range(ndof)]
+    for e in range(lids.shape[0]):
+        s = set(int(c) for c in lids[e])
+        for r in s:
+            cols[r] |= s
+    rowptr = np.zeros(ndof + 1, np.int32)
+    rowptr[1:] = np.cumsum([len(c) for c in cols])
+    colind = np.array([c for cs in cols for c in sorted(cs)], np.int32)
+    return rowptr, colind
+
+
+def assemble(blk, el, fixed=None):
+    """Element arrays -> dict(rowptr, colind, crs_vals, res, S_vals, S_res [global]); fixed rows are zero rows (what
+    assemble_jacres(..., overwrite=True) leaves).  The scales assemble as the values do: sums of the element scales."""
+    lids, nd = blk.lids, blk.ndof
+    rowptr, colind = build_graph(nd, lids)
+    rows = np.repeat(np.arange(nd), np.diff(rowptr))
+    key = rows.astype(np.int64) * nd + colind
+    ek = lids[:, :, None].astype(np.int64) * nd + lids[:, None, :]
+    idx = np.searchsorted(key, ek)
+    assert np.array_equal(key[idx], ek)
+    free = np.ones(nd, bool) if fixed is None else ~np.asarray(fixed, bool)
+    mr, mj = free[lids], np.broadcast_to(free[lids][:, :, None], ek.shape)
+    out = dict(rowptr=rowptr, colind=colind)
+    for name, loc, glob, size in (("res", "local_res", lids, nd), ("S_res", "S_res", lids, nd)):
+        a = np.zeros(size, LD)
+        np.add.at(a, glob[mr], el[loc][mr])
+        out[name] = a
+    for name, loc in (("crs_vals", "local_J"), ("S_vals", "S_J")):
+        a = np.zeros(len(colind), LD)
+        np.add.at(a, idx[mj], el[loc][mj])
+        out[name] = a
+    return out
+
+
+def matvec(g, X, transpose=False):
+    """(A X[k], S of it) for the rows of X [K][ndof] with the assembled matrix of g (longdouble)."""
+    X = np.atleast_2d(np.asarray(X)).astype(LD)
+    nd = len(g["rowptr"]) - 1
+    rows = np.repeat(np.arange(nd), np.diff(g["rowptr"]))
+    r, c = (g["colind"], rows) if transpose else (rows, g["colind"])
+    Y, SY = np.zeros(X.shape, LD), np.zeros(X.shape, LD)
+    for k in range(X.shape[0]):
+        np.add.at(Y[k], r, g["crs_vals"] * X[k, c])
+        np.add.at(SY[k], r, g["S_vals"] * np.abs(X[k, c]))
+    return Y, SY
+
+
+def diagonal(g):
+    nd = len(g["rowptr"]) - 1
+    rows = np.repeat(np.arange(nd), np.diff(g["rowptr"]))
+    on = rows == g["colind"]
+    d, s = np.zeros(nd, LD), np.zeros(nd, LD)
+    d[rows[on]], s[rows[on]] = g["crs_vals"][on], g["S_vals"][on]
+    return d, s
+
+
+# ---- the criterion ----------------------------------------------------------------------------------------------------------
+def distance(got, ref, S):
+    """max over ALL entries of |got - ref| / (2^-53 S); inf if an entry with S == 0 is not exactly 0.0, and inf if any
+    entry of got is not finite (a NaN must not pass for want of an ordering)."""
+    got, ref, S = np.asarray(got), np.asarray(ref), np.asarray(S)
+    assert got.shape == ref.shape == S.shape, (got.shape, ref.shape, S.shape)
+    assert np.all(np.isfinite(ref)) and np.all(np.isfinite(S)), "the yardstick itself is not finite"
+    if not np.all(np.isfinite(got)):
+        return float("inf")
+    zero = S == 0
+    if np.any(got[zero] != 0.0) or np.any(ref[zero] != 0):
+        return float("inf")
+    if zero.all():
+        return 0.0
+    d = np.abs(got[~zero].astype(LD) - ref[~zero]) / (LD(EPS64) * S[~zero])
+    d = float(d.max())
+    return d if d == d else float("inf")
+
+
+# ---- the cases: shapes, input families, data ---------------------------------------------------------------------------------
+TABLEAU = dict(butcher_A=np.array([[0.5, 0.0], [0.3, 0.7]]), butcher_b=np.array([0.4, 0.6]),
+               bdf=np.array([1.5, -2.0, 0.5]), stage=1)        # the two-stage tableau of tests/test_multi_gpu.py
+
+SHAPES = {  # module -> (name, dim, ncell, orders)
+    "thermal": [("Q1 quad", 2, (3, 2), (1,)), ("Q2 quad", 2, (3, 2), (2,)), ("Q3 quad", 2, (2, 2), (3,)),
+                ("Q4 quad", 2, (2, 2), (4,)), ("Q1 hex", 3, (2, 2, 2), (1,)), ("Q2 hex", 3, (2, 2, 2), (2,))],
+    "navierstokes": [("2-D Q2/Q1", 2, (3, 2), (2, 1, 2)), ("3-D Q1/Q1", 3, (2, 2, 2), (1, 1, 1, 1)),
+                     ("3-D Q2/Q1", 3, (2, 1, 1), (2, 1, 2, 2))],
+    "linearelasticity": [("2-D Q1", 2, (3, 2), (1, 1)), ("2-D Q2", 2, (3, 2), (2, 2)), ("3-D Q1", 3, (2, 2, 2), (1, 1, 1)),
+                         ("3-D Q2", 3, (2, 1, 1), (2, 2, 2))],
+}
+FAMILIES = ["unit", "stretched aligned", "stretched sheared", "stretched warped", "units small", "units large"]
+# the terms of thermal that only the point engine has, on the unit family's inputs: (b . grad e, v) and kappa = 1 + e*e
+THERMAL_ONLY = ["unit advection", "unit nonlinear"]
+
+
+def families(module):
+    return FAMILIES + {"thermal": THERMAL_ONLY, "navierstokes": ["rest"], "linearelasticity": ["unit plane stress"]}.get(module, [])
+
+
+def transients(module, family):
+    """steady and stage 1; the nonlinear diffusion's oracle (oracle_lib.assemble_thermal_fields) is steady only."""
+    return (False,) if family == "unit nonlinear" else (False, True)
+
+
+def sinprod_text(spec, dim):
+    """("sinprod", amp, freq) as a deck string."""
+    return "*".join([repr(float(spec[1]))] + ["sin(%r*%s)" % (float(spec[2][d]), "xyz"[d]) for d in range(dim)])
+
+
+def map_vertices(v, family):
+    """The family's geometry from the unit-box vertices v [nv][dim] (doubles; the yardstick takes them as exact)."""
+    dim = v.shape[1]
+    v = v.copy()
+    warp = v.copy()
+    warp[:, 0] += 0.06 * np.sin(1.3 * v[:, 1] + 0.4) + (0.04 * v[:, 2] ** 2 if dim == 3 else 0.0)
+    warp[:, 1] += 0.05 * np.cos(1.1 * v[:, 0]) * (1 + 0.5 * v[:, 1])
+    if dim == 3:
+        warp[:, 2] += 0.05 * v[:, 0] * v[:, 1] + 0.03 * np.sin(2.0 * v[:, 2])
+    stretch = np.array([1.0, 1e-3, 1.0])[:dim]                  # 1 : 1000 boxes
+    if family in ("unit", "rest", "unit plane stress") + tuple(THERMAL_ONLY):
+        return warp
+    if family == "stretched aligned":
+        return v * stretch
+    if family == "stretched sheared":
+        A = np.eye(dim) + 0.25 * np.array([[0.3, 0.8, -0.4], [-0.5, 0.2, 0.6], [0.7, -0.3, 0.1]])[:dim, :dim]
+        return (v * stretch) @ A.T + 0.3
+    if family == "stretched warped":
+        return warp * stretch
+    if family == "units small":
+        return warp * 1e-3
+    if family == "units large":
+        return warp * 1e3
+    raise ValueError(family)
+
+
+def case_data(module, family, dim, ndof, dof_var, transient, seed=97):
+    """-> (u, tr, params): the state, the transient dict (or None) and the module's functions / parameters."""
+    rng = np.random.default_rng(seed)
+    # "units small": lengths 1e-3 with coefficients 1e+6; "units large": lengths 1e+3 with coefficients 1e-6
+    L = {"units small": 1e-3, "units large": 1e3}.get(family, 1.0)          # length scale
+    coef = {"units small": 1e6, "units large": 1e-6}.get(family, 1.0)
+    amp = 1e3 if family.startswith("units") else 1.0
+    u = amp * rng.uniform(-1, 1, ndof)
+    tr = None
+    if transient:
+        # dt scaled to match: the diffusive time L^2 / kappa (thermal), the advective time L / |u| (navierstokes)
+        dt = 0.05 * {"thermal": L * L / coef, "navierstokes": L / amp, "linearelasticity": 1.0}[module]
+        tr = dict(TABLEAU, dt=dt, u_prev=amp * rng.uniform(-1, 1, (ndof, 2)), u_stage=amp * rng.uniform(-1, 1, (ndof, 2)))
+    fr = [f / L for f in (1.3, 0.7, 2.1)[:dim]]
+    if module == "thermal":
+        P = dict(source=("sinprod", 3.0 * amp * coef / (L * L), fr), diffusion=1.7 * coef, rho=1.3, cp=0.7, adv=None)
+        if family == "unit advection":
+            P["adv"] = (0.8, -0.5, 0.3)[:dim]
+        if family == "unit nonlinear":
+            P["diffusion"], P["diffusion_text"] = (lambda e: 1 + e * e), "1+e*e"
+    elif module == "navierstokes":
+        P = {"source ux": 0.3, "source uy": ("sinprod", 1.0, fr), "source uz": -0.2, "viscosity": 0.05 * coef,
+             "density": 1.3, "useSUPG": 1, "usePSPG": 1, "fix_uz_offsets": 0}
+        if family == "rest":                                    # the other side of nvel > 1e-12: every velocity dof 0
+            P["fix_uz_offsets"] = 1                             # ... and the uz rows through their own offsets
+            for a in (u,) + ((tr["u_prev"], tr["u_stage"]) if tr else ()):
+                a[np.asarray(dof_var) != 1] = 0.0
+    else:
+        P = {"lambda": 1.1 * coef, "mu": 0.6 * coef, "source dx": 0.3, "source dy": ("sinprod", 1.0, fr), "source dz": -0.2,
+             "incplanestress": 1 if family == "unit plane stress" else 0}   # 2-D: lambda = 2 mu (:990-1000); 3-D ignores it
+    return u, tr, P
+
+
+_CASES = {}
+
+
+def build_case(meshlib, module, shape, family, transient):
+    """One case, cached: mesh (meshlib: tests/oracle_lib.py, used for the structured mesh and its integer maps only),
+    data, the yardstick's element arrays `el` and global arrays `g`."""
+    key = (module, shape, family, transient)
+    if key in _CASES:
+        return _CASES[key]
+    name, dim, ncell, orders = shape
+    if module == "thermal":
+        m = meshlib.mesh_structured(dim, orders[0], ncell)
+        m["dof_var"] = np.zeros(m["ndof"], np.int32)
+        fixed = m["boundary"].copy()
+    else:
+        m = meshlib.mesh_multi(dim, ncell, [0] * len(orders), list(orders))
+        pinned = (m["side_mask"] & 0b1100) != 0                               # strong Dirichlet rows on two sides
+        fixed = (pinned & (m["dof_var"] != 1) if module == "navierstokes" else pinned).astype(np.uint8)
+    m["verts"] = map_vertices(m["verts"], family)
+    m["nodes"] = np.ascontiguousarray(m["verts"][m["cell2vert"]])
+    qdeg = 2 * orders[0]
+    u, tr, P = case_data(module, family, dim, m["ndof"], m["dof_var"], transient)
+    quirk = module == "navierstokes" and dim == 3 and not P["fix_uz_offsets"]
+    blk = Block(m, qdeg, order=orders[0] if module == "thermal" else None, test_var=[0, 1, 2, 2] if quirk else None)
+    blk.check_ordering()
+    el = element_arrays(blk, module, P, u, tr)
+    c = dict(module=module, shape=shape, family=family, m=m, dim=dim, orders=orders, qdeg=qdeg, u=u, tr=tr, P=P, fixed=fixed,
+             blk=blk, el=el, g=assemble(blk, el, fixed))
+    _CASES[key] = c
+    return c

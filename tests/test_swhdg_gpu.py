@@ -276,12 +276,48 @@ def test_batched_condensation(oracle):
         g_ref = res[:, ni:] - (Alu @ X[:, :, nt:])[..., 0]
         for got, ref in ((S.cpu().numpy(), S_ref), (g.cpu().numpy(), g_ref), (du.cpu().numpy(), X[:, :, nt])):
             assert np.abs(got - ref).max() < 1e-10 * np.abs(ref).max()
+        # the same elimination (Gauss-Jordan on [A_uu | A_ul | r_u], partial pivoting) in 80-bit arithmetic
+        Sx, gx, dux, nswap = condense_longdouble(blocks, res, ni, nt)
+        for name, got, ref in (("S", S, Sx), ("g", g, gx), ("du", du, dux)):
+            err = float(np.abs(got.cpu().numpy() - ref).max() / np.abs(ref).max())
+            print("condense (%d, %d) %s: %.3e (bound 1e-10), row exchanges per element >= %d" % (ni, nt, name, err, nswap))
+            assert err < 1e-10, (ni, nt, name)
+        return nswap
 
-    for ni, nt in ((12, 24), (5, 3), (32, 31), (1, 1)):
+    def condense_longdouble(blocks, res, ni, nt):
+        E, n = res.shape
+        M = np.concatenate([blocks[:, :ni, :], res[:, :ni, None]], axis=2).astype(np.longdouble)  # [E][ni][n + 1]
+        ar = np.arange(E)
+        nswap = np.zeros(E, dtype=int)
+        for k in range(ni):
+            piv = k + np.argmax(np.abs(M[:, k:, k]), axis=1)
+            nswap += piv != k
+            rk, rp = M[ar, k].copy(), M[ar, piv].copy()
+            M[ar, piv], M[ar, k] = rk, rp
+            M[:, k] = M[:, k] / M[:, k, k:k + 1]
+            f = M[:, :, k].copy()
+            f[:, k] = 0
+            M = M - f[:, :, None] * M[:, k:k + 1, :]
+        X = M[:, :, ni:]                                                                          # [X_ul | x_r]
+        low = np.concatenate([blocks[:, ni:, :], res[:, ni:, None]], axis=2).astype(np.longdouble)
+        Sg = low[:, :, ni:] - np.einsum("eai,eib->eab", low[:, :, :ni], X)
+        return (Sg[:, :, :nt].astype(np.float64), Sg[:, :, nt].astype(np.float64), X[:, :, nt].astype(np.float64),
+                int(nswap.min()))
+
+    # (5, 40), (30, 33), (1, 62): more than kCondMaxTrace = 32 trace rows, the loop of condense.hip that re-reads them
+    for ni, nt in ((12, 24), (5, 3), (32, 31), (1, 1), (5, 40), (30, 33), (1, 62)):
         E = 37
         blocks = rng.uniform(-1, 1, (E, ni + nt, ni + nt))
         blocks[:, np.arange(ni), np.arange(ni)] += 0.1 * ni * np.sign(rng.uniform(-1, 1, (E, ni)))  # pivoting still matters
         check(blocks, rng.uniform(-1, 1, (E, ni + nt)), ni, nt)
+        # second family: the interior rows of a strictly diagonally dominant block (no exchange needed, its pivots are the
+        # diagonal) rotated by one, row i <- row i + 1: the dominant entry of column k then sits in row k - 1, which the
+        # elimination has used already for k >= 1, and in the last row for k = 0, so every step but the last exchanges rows
+        blocks = rng.uniform(-1, 1, (E, ni + nt, ni + nt))
+        blocks[:, np.arange(ni), np.arange(ni)] = (ni + 1.0) * np.sign(rng.uniform(-1, 1, (E, ni)))
+        blocks[:, :ni] = np.roll(blocks[:, :ni], -1, axis=1)
+        nswap = check(blocks, rng.uniform(-1, 1, (E, ni + nt)), ni, nt)
+        assert nswap >= ni - 1, (ni, nt, nswap)
     # the real thing
     m, u, lam, st, ff = hdg_case(oracle, ncell=(4, 3), seed=15)
     tr = transient_state(rng, m["ndof"], u)
