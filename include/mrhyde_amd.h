@@ -179,6 +179,26 @@ int mha_get_graph(mha_context *ctx, int32_t *rowptr_host, int32_t *colind_host);
  * MHA_ASSEMBLE_DETERMINISTIC, and the 3-D Q2/Q1/Q2/Q2/Q2 element (its LDS need).  Strong Dirichlet rows and the generic
  * "Flux" condition work per variable as on every block.                                                             */
 #define MHA_PHYSICS_NAVIERSTOKES_CDR (MHA_PHYSICS_LINEARELASTICITY_THERMAL + 2)
+/* helmholtz, the frequency-domain wave module (src/physics/helmholtz.cpp): the complex field as two HGRAD variables
+ * ureal, uimag (:24-27) of the SAME order (the reference indexes uimag's basis with ureal's loop index, :155-159;
+ * different orders are refused), 2-D and 3-D.  Volume terms (:175-193, the non-fractional branch) with vr = vi = N_i:
+ *   row ureal: -omega2r (ur + ui) + omega2i (ui - ur) - (source_r + source_i)   against the test value,
+ *              c2r_d (d_d ur + d_d ui) - c2i_d (d_d ui - d_d ur)                against its d-th derivative;
+ *   row uimag: -omega2r (ui - ur) - omega2i (ur + ui) - (source_i - source_r),
+ *              c2r_d (d_d ui - d_d ur) + c2i_d (d_d ur + d_d ui)
+ * -- the reference's own sums of real and imaginary test parts, kept as they are.  No time-derivative term.  Functions,
+ * all 0 by default (:41-70): "c2r_x", "c2i_x", "c2r_y", "c2i_y", "c2r_z", "c2i_z", "omega2r", "omega2i", "source_r",
+ * "source_i" (constants, arrays, closed forms, deck strings in the coordinates with named helpers); on sides also
+ * "robin_alpha_r", "robin_alpha_i", "source_r_side", "source_i_side".  "omegar", "omegai", "alphaHr", "alphaHi",
+ * "alphaTr", "alphaTi", "freqExp" are accepted and read by no built term.  A MHA_BC_NEUMANN boundary group is the
+ * Robin condition of boundaryResidual (:254-419, non-fractional): alpha u + du/dn - source - c2 du/dn on both rows, its
+ * Jacobian holding the N_a (grad N_b . n) blocks between all four variable pairs.  computeFlux is empty in the
+ * reference (:430-433): mha_compute_flux returns zeros.  Runs on the point engine (MHA_PATH_AUTO / _ROW_GATHER /
+ * _POINT_ENGINE / _LOCAL_THEN_SCATTER) and in the matrix-free products.  Refused with MHA_ERR_INVALID: the parameter
+ * "fractional" != 0 (its volume form names 13 functions), 1-D, MHA_PATH_ROW_OWNER, MHA_ASSEMBLE_DETERMINISTIC, deck
+ * strings that read the solution fields, weak-Dirichlet and interface groups, and any of the ten volume functions given
+ * as a volume MHA_FUNC_IP_ARRAY while a Neumann group exists.                                                        */
+#define MHA_PHYSICS_HELMHOLTZ (MHA_PHYSICS_LINEARELASTICITY_THERMAL + 3)
 int mha_physics_select(mha_context *ctx, int physics_id);
 #define MHA_FUNC_CONSTANT 0
 #define MHA_FUNC_IP_ARRAY 1     /* dev pointer to [E][numip] f64                    */
@@ -559,7 +579,7 @@ int mha_boundary_view(mha_context *ctx, int group_id, const char *name, void **d
  * (navierstokes.cpp:45-46) and "fix_uz_offsets": the reference scatters the 3-D uz momentum
  * block through uy's offsets (navierstokes.cpp:688); 0 (default) reproduces that, 1 uses uz's;
  * shallowwaterHybridized: "g" (shallowwaterHybridized.cpp:72, default 9.81); navierstokes + cdr: navierstokes' three;
- * cdr: none.                                                                                      */
+ * cdr: none; helmholtz: "fractional" (helmholtz.cpp:22), accepted at 0 only.                       */
 /* porousMixed (porousMixed.cpp:46-120) also takes: "use permeability data" (Kinv_xx = Kinv_yy = Kinv_zz = 1 / data(elem, 0)
  * from the block's element data, in place of the Kinv_* functions, updatePerm :550-563; total_mobility still divides);
  * "use KL expansion" (Kinv_dd divided by exp(KL_dd), a Karhunen-Loeve field evaluated at every integration point,

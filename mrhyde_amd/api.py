@@ -53,6 +53,11 @@ PHYSICS_LINEARELASTICITY = 6
 PHYSICS_LINEARELASTICITY_THERMAL = 7
 PHYSICS_CDR = 8
 PHYSICS_NAVIERSTOKES_CDR = 9
+# helmholtz: ureal, uimag (HGRAD, one order), the frequency-domain wave module.  Its id is the first with two decimal
+# digits.  PHYSICS_IDS stays the table of the one-digit ids (tests/test_cdr.py pins its largest value); Block looks a
+# name up in ALL_PHYSICS_IDS, which holds every module.
+PHYSICS_HELMHOLTZ = 10
+ALL_PHYSICS_IDS = dict(PHYSICS_IDS, helmholtz=PHYSICS_HELMHOLTZ)
 PATH_POINT_ENGINE = 4
 PATH_ROW_GATHER = 5
 BC_NEUMANN, BC_WEAK_DIRICHLET, BC_FLUX = 1, 2, 3
@@ -749,9 +754,9 @@ class Block:
         self.dim, self.order = dim, order
         self._keep = []
         if physics is not None:
-            if physics not in PHYSICS_IDS:
+            if physics not in ALL_PHYSICS_IDS:
                 raise ValueError(physics)
-            _check(lib.mha_physics_select(self._h, PHYSICS_IDS[physics]))
+            _check(lib.mha_physics_select(self._h, ALL_PHYSICS_IDS[physics]))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -397,6 +397,12 @@ void AssemblyManager::selectPhysics(int physics_id) {
                 "navierstokes+cdr needs the " << dim_ + 2 << " HGRAD variables ux, pr, uy" << (dim_ == 3 ? ", uz" : "")
                                                << ", c, in that order");
   }
+  else if (physics_id == MHA_PHYSICS_HELMHOLTZ) {
+    MHA_REQUIRE(expect({MHA_BASIS_HGRAD, MHA_BASIS_HGRAD}) && (dim_ == 2 || dim_ == 3), MHA_ERR_INVALID,
+                "helmholtz needs the two HGRAD variables ureal, uimag in 2-D or 3-D");
+    // the reference indexes uimag's basis with ureal's loop index (helmholtz.cpp:155-159)
+    MHA_REQUIRE(vars_[0].order == vars_[1].order, MHA_ERR_INVALID, "helmholtz needs the same order on ureal and uimag");
+  }
   physics_id_ = physics_id;
   physics_ = import_physics(physics_id, dim_);
   physics_->defineFunctions(functions_);
@@ -557,6 +563,7 @@ void AssemblyManager::assembleJacRes(int flags, int path, const double *u, const
   MHA_REQUIRE(res != nullptr, MHA_ERR_INVALID, "residual vector is null");
   MHA_REQUIRE(!compute_jacobian || crs_vals, MHA_ERR_INVALID, "compute_jacobian set but crs_vals is null");
   bindState(u, u_prev, u_stage);
+  physics_->checkVolumeFunctions(dim_);
   if (engineOnly()) {
     // multi-variable modules (and thermal with its advection term) run on the point engine
     if (path == MHA_PATH_AUTO) path = MHA_PATH_ROW_GATHER;
@@ -1524,6 +1531,13 @@ int AssemblyManager::addBoundaryGroup(const std::string &sidename, int bc_type, 
     MHA_REQUIRE(linearelasticity_boundary_supported(dim_, dim_ * vars_[0].card, side_ref_.nqs), MHA_ERR_INVALID,
                 "linearelasticity boundary terms are not available for " << vars_[0].card << " dofs per component with "
                                                                          << side_ref_.nqs << " side integration points");
+  } else if (physics_id_ == MHA_PHYSICS_HELMHOLTZ) {
+    MHA_REQUIRE(bc_type == MHA_BC_NEUMANN, MHA_ERR_INVALID,
+                "helmholtz: boundary groups are MHA_BC_NEUMANN (the Robin condition of helmholtz.cpp:320-375); "
+                "weak-Dirichlet and interface groups are not built");
+    MHA_REQUIRE(helmholtz_boundary_supported(dim_, n_, side_ref_.nqs), MHA_ERR_INVALID,
+                "helmholtz boundary terms are not available for " << n_ << " dofs per element with " << side_ref_.nqs
+                                                                  << " side integration points");
   } else if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY) {
     MHA_REQUIRE(bc_type == MHA_BC_NEUMANN || bc_type == MHA_BC_WEAK_DIRICHLET, MHA_ERR_INVALID,
                 "linearelasticity: boundary groups are MHA_BC_NEUMANN (traction) or MHA_BC_WEAK_DIRICHLET; the interface "
@@ -1723,6 +1737,10 @@ void AssemblyManager::assembleBoundary(int flags, const double *u, const double 
     for (const auto &g : boundary_groups_)
       MHA_REQUIRE(g->bc_type != MHA_BC_INTERFACE, MHA_ERR_INVALID,
                   "linearelasticity: the interface condition (MHA_BC_INTERFACE) is not built (group '" << g->sidename << "')");
+  if (physics_id_ == MHA_PHYSICS_HELMHOLTZ)
+    for (const auto &g : boundary_groups_)
+      MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX || g->bc_type == MHA_BC_NEUMANN, MHA_ERR_INVALID,
+                  "helmholtz: only MHA_BC_NEUMANN (Robin) groups are built (group '" << g->sidename << "')");
   timedBegin();
   for (size_t gi = 0; gi < boundary_groups_.size(); ++gi) {
     const auto &g = boundary_groups_[gi];

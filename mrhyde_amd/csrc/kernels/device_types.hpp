@@ -314,6 +314,14 @@ struct LeBoundaryDev {
                                // the element's b.n dofs end with those of e): traction on the displacement rows only
 };
 
+// helmholtz::boundaryResidual on a boundary group (kernels/helmholtz_boundary.hip): the ten functions of the Robin
+// condition at the side points (constants, closed forms, deck strings; [num][nqs] arrays for the four side-only ones)
+struct HelmholtzBoundaryDev {
+  // f[0..5]: c2r_x, c2i_x, c2r_y, c2i_y, c2r_z, c2i_z; f[6], f[7]: robin_alpha_r, robin_alpha_i;
+  // f[8], f[9]: source_r_side, source_i_side
+  FuncDesc f[10];
+};
+
 // linearelasticity::getDerivedValues on all elements of a block (kernels/linearelasticity_stress.hip)
 struct LeStressDev {
   int card_u = 0;                  // dofs of one displacement component (the block's first dim variables)

@@ -67,6 +67,13 @@ struct Layout<MHA_PHYSICS_NAVIERSTOKES_CDR, DIM> {
   __host__ __device__ static constexpr int type(int) { return MHA_BASIS_HGRAD; }
 };
 
+// helmholtz: ureal, uimag
+template <int DIM>
+struct Layout<MHA_PHYSICS_HELMHOLTZ, DIM> {
+  static constexpr int nvars = 2, NS = 2 * (1 + DIM);
+  __host__ __device__ static constexpr int type(int) { return MHA_BASIS_HGRAD; }
+};
+
 template <int DIM>
 struct Layout<MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED, DIM> {
   static constexpr int nvars = 3, NS = 3 * (1 + DIM);
@@ -195,5 +202,6 @@ constexpr int geo_size() { return 2 * DIM * DIM + 2 + DIM; }  // J, Ji, det, w, 
     else if constexpr (PHYS == MHA_PHYSICS_LINEARELASTICITY_THERMAL) linearelasticity_thermal_point<DIM, (EXPR != 0)>(pa, F); \
     else if constexpr (PHYS == MHA_PHYSICS_CDR) cdr_point<DIM, EXPR>(pa, F);                                             \
     else if constexpr (PHYS == MHA_PHYSICS_NAVIERSTOKES_CDR) navierstokes_cdr_point<DIM, EXPR>(pa, F);                   \
+    else if constexpr (PHYS == MHA_PHYSICS_HELMHOLTZ) helmholtz_point<DIM, (EXPR != 0)>(pa, F);                          \
     else navierstokes_point<DIM, (EXPR != 0)>(pa, F);                                                                    \
   } while (0)

@@ -251,10 +251,10 @@ void launch_jacobian_apply(const BlockDev &b, const VarLayoutDev &vl, const Phys
     if (overwrite) MHA_HIP(hipMemsetAsync(y, 0, sizeof(double) * b.nrows, stream));
     return;
   }
-  static_assert(MHA_PHYSICS_NAVIERSTOKES_CDR < 10, "the switch key holds one decimal digit of module id");
+  static_assert(MHA_PHYSICS_HELMHOLTZ < 100, "the switch key holds two decimal digits of module id");
 #define MHA_APPLY_CASE(D, P) \
-  case D * 10 + P: launch_typed<D, P>(b, vl, pp, tm, x, y, transpose, overwrite, stream, lds_bytes, waves); break;
-  switch (b.dim * 10 + pp.physics) {
+  case D * 100 + P: launch_typed<D, P>(b, vl, pp, tm, x, y, transpose, overwrite, stream, lds_bytes, waves); break;
+  switch (b.dim * 100 + pp.physics) {
     MHA_APPLY_CASE(2, MHA_PHYSICS_THERMAL)
     MHA_APPLY_CASE(3, MHA_PHYSICS_THERMAL)
     MHA_APPLY_CASE(2, MHA_PHYSICS_POROUS_MIXED)
@@ -271,6 +271,8 @@ void launch_jacobian_apply(const BlockDev &b, const VarLayoutDev &vl, const Phys
     MHA_APPLY_CASE(3, MHA_PHYSICS_CDR)
     MHA_APPLY_CASE(2, MHA_PHYSICS_NAVIERSTOKES_CDR)
     MHA_APPLY_CASE(3, MHA_PHYSICS_NAVIERSTOKES_CDR)
+    MHA_APPLY_CASE(2, MHA_PHYSICS_HELMHOLTZ)
+    MHA_APPLY_CASE(3, MHA_PHYSICS_HELMHOLTZ)
     MHA_APPLY_CASE(2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED)
     default: MHA_REQUIRE(false, MHA_ERR_INVALID, "no Jacobian-product kernel for physics " << pp.physics << " in " << b.dim << "-D");
   }

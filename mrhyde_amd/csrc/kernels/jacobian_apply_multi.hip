@@ -309,12 +309,12 @@ void launch_jacobian_apply_multi(const BlockDev &b, const VarLayoutDev &vl, cons
     if (overwrite) MHA_HIP(hipMemset2DAsync(y, sizeof(double) * ldy, 0, sizeof(double) * b.nrows, nvec, stream));
     return;
   }
-  static_assert(MHA_PHYSICS_NAVIERSTOKES_CDR < 10, "the switch key holds one decimal digit of module id");
+  static_assert(MHA_PHYSICS_HELMHOLTZ < 100, "the switch key holds two decimal digits of module id");
 #define MHA_APPLY_CASE(D, P)                                                                                              \
-  case D * 10 + P:                                                                                                        \
+  case D * 100 + P:                                                                                                       \
     launch_typed<D, P>(b, vl, pp, tm, nvec, x, ldx, y, ldy, transpose, overwrite, stream, lds_bytes, waves, vectors);     \
     break;
-  switch (b.dim * 10 + pp.physics) {
+  switch (b.dim * 100 + pp.physics) {
     MHA_APPLY_CASE(2, MHA_PHYSICS_THERMAL)
     MHA_APPLY_CASE(3, MHA_PHYSICS_THERMAL)
     MHA_APPLY_CASE(2, MHA_PHYSICS_POROUS_MIXED)
@@ -331,6 +331,8 @@ void launch_jacobian_apply_multi(const BlockDev &b, const VarLayoutDev &vl, cons
     MHA_APPLY_CASE(3, MHA_PHYSICS_CDR)
     MHA_APPLY_CASE(2, MHA_PHYSICS_NAVIERSTOKES_CDR)
     MHA_APPLY_CASE(3, MHA_PHYSICS_NAVIERSTOKES_CDR)
+    MHA_APPLY_CASE(2, MHA_PHYSICS_HELMHOLTZ)
+    MHA_APPLY_CASE(3, MHA_PHYSICS_HELMHOLTZ)
     MHA_APPLY_CASE(2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED)
     default: MHA_REQUIRE(false, MHA_ERR_INVALID, "no Jacobian-product kernel for physics " << pp.physics << " in " << b.dim << "-D");
   }

@@ -244,10 +244,10 @@ void launch_jacobian_diagonal(const BlockDev &b, const VarLayoutDev &vl, const P
     if (overwrite) MHA_HIP(hipMemsetAsync(d, 0, sizeof(double) * b.nrows, stream));
     return;
   }
-  static_assert(MHA_PHYSICS_NAVIERSTOKES_CDR < 10, "the switch key holds one decimal digit of module id");
+  static_assert(MHA_PHYSICS_HELMHOLTZ < 100, "the switch key holds two decimal digits of module id");
 #define MHA_DIAG_CASE(D, P) \
-  case D * 10 + P: launch_typed<D, P>(b, vl, pp, tm, d, overwrite, stream, lds_bytes, waves); break;
-  switch (b.dim * 10 + pp.physics) {
+  case D * 100 + P: launch_typed<D, P>(b, vl, pp, tm, d, overwrite, stream, lds_bytes, waves); break;
+  switch (b.dim * 100 + pp.physics) {
     MHA_DIAG_CASE(2, MHA_PHYSICS_THERMAL)
     MHA_DIAG_CASE(3, MHA_PHYSICS_THERMAL)
     MHA_DIAG_CASE(2, MHA_PHYSICS_POROUS_MIXED)
@@ -264,6 +264,8 @@ void launch_jacobian_diagonal(const BlockDev &b, const VarLayoutDev &vl, const P
     MHA_DIAG_CASE(3, MHA_PHYSICS_CDR)
     MHA_DIAG_CASE(2, MHA_PHYSICS_NAVIERSTOKES_CDR)
     MHA_DIAG_CASE(3, MHA_PHYSICS_NAVIERSTOKES_CDR)
+    MHA_DIAG_CASE(2, MHA_PHYSICS_HELMHOLTZ)
+    MHA_DIAG_CASE(3, MHA_PHYSICS_HELMHOLTZ)
     MHA_DIAG_CASE(2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED)
     default: MHA_REQUIRE(false, MHA_ERR_INVALID, "no Jacobian-diagonal kernel for physics " << pp.physics << " in " << b.dim << "-D");
   }

@@ -149,6 +149,11 @@ bool linearelasticity_boundary_supported(int dim, int n, int nqs);
 void launch_linearelasticity_boundary(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd,
                                       const LeBoundaryDev &le, const TimeDev &tm, const ElemOut &out, hipStream_t stream);
 
+// helmholtz_boundary.hip: helmholtz::boundaryResidual (the Robin condition of a Neumann group, both rows and the Jacobian)
+bool helmholtz_boundary_supported(int dim, int n, int nqs);
+void launch_helmholtz_boundary(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd,
+                               const HelmholtzBoundaryDev &hb, const TimeDev &tm, const ElemOut &out, hipStream_t stream);
+
 // linearelasticity_stress.hip: linearelasticity::getDerivedValues (stress tensor, "VM stress", "MAG stress")
 void launch_linearelasticity_stress(const BlockDev &b, const LeStressDev &a, hipStream_t stream);
 

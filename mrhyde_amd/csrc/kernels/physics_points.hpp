@@ -325,6 +325,43 @@ __device__ __forceinline__ void navierstokes_cdr_point(const PointArgs<DIM> &a, 
   cdr_row<DIM, EXPR, true>(a, (DIM + 1) * (1 + DIM), F);
 }
 
+// helmholtz, the frequency-domain wave module (reference: src/physics/helmholtz.cpp:175-193, the non-fractional branch);
+// myvars {ureal, uimag}, both HGRAD of ONE order (the host refuses two); functions {c2r_x, c2i_x, c2r_y, c2i_y, c2r_z,
+// c2i_z, omega2r, omega2i, source_r, source_i}, all 0 by default (:41-70).  The reference tests row ureal with
+// (vr, vi) = (ureal's basis i, uimag's basis i) and adds real and imaginary test parts (its own comment: "this residual
+// makes no sense to me"); with one order vr = vi = N_i and the two rows are
+//   value slot of ureal     -omega2r (ur + ui) + omega2i (ui - ur) - (source_r + source_i)
+//   gradient slot d         c2r_d (d_d ur + d_d ui) - c2i_d (d_d ui - d_d ur)
+//   value slot of uimag     -omega2r (ui - ur) - omega2i (ur + ui) - (source_i - source_r)
+//   gradient slot d         c2r_d (d_d ui - d_d ur) + c2i_d (d_d ur + d_d ui)
+// kept as they are: the reference's gold depends on them.  No time-derivative term.  EXPR: 0 constants / closed forms /
+// arrays, 1 deck strings in the coordinates, evaluated in a loop that is NOT unrolled (one inlined interpreter).
+template <int DIM, bool EXPR>
+__device__ __forceinline__ void helmholtz_point(const PointArgs<DIM> &a, Dual *F) {
+  constexpr int S = 1 + DIM, NF = 2 * DIM + 4;
+  const PhysParamsDev &pp = *a.pp;
+  // k: 0 .. 2 DIM - 1 the c2 pairs of the directions, then omega2r, omega2i, source_r, source_i (table entries 6 .. 9)
+  double fv[NF];
+  if constexpr (EXPR) {
+#pragma nounroll
+    for (int k = 0; k < NF; ++k) fv[k] = eval_func<DIM, true>(pp.f[k < 2 * DIM ? k : k + 6 - 2 * DIM], a.e, a.q, a.nq, a.x);
+  } else {
+#pragma unroll
+    for (int k = 0; k < NF; ++k) fv[k] = eval_func<DIM, false>(pp.f[k < 2 * DIM ? k : k + 6 - 2 * DIM], a.e, a.q, a.nq, a.x);
+  }
+  const double w2r = fv[2 * DIM], w2i = fv[2 * DIM + 1], sr = fv[2 * DIM + 2], si = fv[2 * DIM + 3];
+  const Dual ur = a.U[0], ui = a.U[S];
+  F[0] = (ui - ur) * w2i - (ur + ui) * w2r - (sr + si);
+  F[S] = (ur - ui) * w2r - (ur + ui) * w2i - (si - sr);
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    const Dual gr = a.U[1 + d], gi = a.U[S + 1 + d];
+    const double cr = fv[2 * d], ci = fv[2 * d + 1];
+    F[1 + d] = (gr + gi) * cr - (gi - gr) * ci;
+    F[S + 1 + d] = (gi - gr) * cr + (gr + gi) * ci;
+  }
+}
+
 // linearelasticity (reference: src/physics/linearelasticity.cpp:92-240 with computeStress :913-1099, onside = false);
 // myvars {dx, dy[, dz]}; functions {lambda, mu, source dx, source dy, source dz}; p = {incplanestress}.
 // sigma = lambda tr(grad u) I + mu (grad u + grad u^T); row d gets sum_j sigma_dj d_j v - source_d v.  incplanestress

@@ -691,26 +691,28 @@ void launch_typed(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev
 void launch_point_engine(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp, const TimeDev &tm,
                          const ElemOut &out, const void *slot, int slot_bytes, hipStream_t stream) {
   if (b.e_count <= 0) return;
-  static_assert(MHA_PHYSICS_NAVIERSTOKES_CDR < 10, "the switch key holds one decimal digit of module id");
-  const int key = b.dim * 10 + (pp.physics < 0 ? -pp.physics : pp.physics);
+  static_assert(MHA_PHYSICS_HELMHOLTZ < 100, "the switch key holds two decimal digits of module id");
+  const int key = b.dim * 100 + (pp.physics < 0 ? -pp.physics : pp.physics);
   switch (key) {
-    case 20 + MHA_PHYSICS_THERMAL: launch_typed<2, MHA_PHYSICS_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 30 + MHA_PHYSICS_THERMAL: launch_typed<3, MHA_PHYSICS_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 20 + MHA_PHYSICS_POROUS_MIXED: launch_typed<2, MHA_PHYSICS_POROUS_MIXED>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 30 + MHA_PHYSICS_POROUS_MIXED: launch_typed<3, MHA_PHYSICS_POROUS_MIXED>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 20 + MHA_PHYSICS_NAVIERSTOKES: launch_typed<2, MHA_PHYSICS_NAVIERSTOKES>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 30 + MHA_PHYSICS_NAVIERSTOKES: launch_typed<3, MHA_PHYSICS_NAVIERSTOKES>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 20 + MHA_PHYSICS_NAVIERSTOKES_THERMAL: launch_typed<2, MHA_PHYSICS_NAVIERSTOKES_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 30 + MHA_PHYSICS_NAVIERSTOKES_THERMAL: launch_typed<3, MHA_PHYSICS_NAVIERSTOKES_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 20 + MHA_PHYSICS_LINEARELASTICITY: launch_typed<2, MHA_PHYSICS_LINEARELASTICITY>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 30 + MHA_PHYSICS_LINEARELASTICITY: launch_typed<3, MHA_PHYSICS_LINEARELASTICITY>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 20 + MHA_PHYSICS_LINEARELASTICITY_THERMAL: launch_typed<2, MHA_PHYSICS_LINEARELASTICITY_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 30 + MHA_PHYSICS_LINEARELASTICITY_THERMAL: launch_typed<3, MHA_PHYSICS_LINEARELASTICITY_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 20 + MHA_PHYSICS_CDR: launch_typed<2, MHA_PHYSICS_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 30 + MHA_PHYSICS_CDR: launch_typed<3, MHA_PHYSICS_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 20 + MHA_PHYSICS_NAVIERSTOKES_CDR: launch_typed<2, MHA_PHYSICS_NAVIERSTOKES_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 30 + MHA_PHYSICS_NAVIERSTOKES_CDR: launch_typed<3, MHA_PHYSICS_NAVIERSTOKES_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 20 + MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED: launch_typed<2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 200 + MHA_PHYSICS_THERMAL: launch_typed<2, MHA_PHYSICS_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 300 + MHA_PHYSICS_THERMAL: launch_typed<3, MHA_PHYSICS_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 200 + MHA_PHYSICS_POROUS_MIXED: launch_typed<2, MHA_PHYSICS_POROUS_MIXED>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 300 + MHA_PHYSICS_POROUS_MIXED: launch_typed<3, MHA_PHYSICS_POROUS_MIXED>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 200 + MHA_PHYSICS_NAVIERSTOKES: launch_typed<2, MHA_PHYSICS_NAVIERSTOKES>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 300 + MHA_PHYSICS_NAVIERSTOKES: launch_typed<3, MHA_PHYSICS_NAVIERSTOKES>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 200 + MHA_PHYSICS_NAVIERSTOKES_THERMAL: launch_typed<2, MHA_PHYSICS_NAVIERSTOKES_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 300 + MHA_PHYSICS_NAVIERSTOKES_THERMAL: launch_typed<3, MHA_PHYSICS_NAVIERSTOKES_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 200 + MHA_PHYSICS_LINEARELASTICITY: launch_typed<2, MHA_PHYSICS_LINEARELASTICITY>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 300 + MHA_PHYSICS_LINEARELASTICITY: launch_typed<3, MHA_PHYSICS_LINEARELASTICITY>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 200 + MHA_PHYSICS_LINEARELASTICITY_THERMAL: launch_typed<2, MHA_PHYSICS_LINEARELASTICITY_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 300 + MHA_PHYSICS_LINEARELASTICITY_THERMAL: launch_typed<3, MHA_PHYSICS_LINEARELASTICITY_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 200 + MHA_PHYSICS_CDR: launch_typed<2, MHA_PHYSICS_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 300 + MHA_PHYSICS_CDR: launch_typed<3, MHA_PHYSICS_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 200 + MHA_PHYSICS_NAVIERSTOKES_CDR: launch_typed<2, MHA_PHYSICS_NAVIERSTOKES_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 300 + MHA_PHYSICS_NAVIERSTOKES_CDR: launch_typed<3, MHA_PHYSICS_NAVIERSTOKES_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 200 + MHA_PHYSICS_HELMHOLTZ: launch_typed<2, MHA_PHYSICS_HELMHOLTZ>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 300 + MHA_PHYSICS_HELMHOLTZ: launch_typed<3, MHA_PHYSICS_HELMHOLTZ>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
+    case 200 + MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED: launch_typed<2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
     default: MHA_REQUIRE(false, MHA_ERR_INVALID, "no point-engine kernel for physics " << pp.physics << " in " << b.dim << "-D");
   }
 }

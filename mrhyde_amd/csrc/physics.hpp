@@ -69,6 +69,8 @@ class PhysicsBase {
   virtual void setWorkset(Workset *w) { wkset = w; }
   // true when the current settings need terms only the point-engine form of the module has
   virtual bool pointEngineOnly() const { return false; }
+  // refusals of the module's volume functions that an assembly states before it writes anything
+  virtual void checkVolumeFunctions(int /*dim*/) const {}
   // scalar settings a module reads from its parameter list in the reference constructor
   virtual void setParameter(const std::string &name, double) {
     throw Error(MHA_ERR_INVALID, "physics module '" + label + "' has no parameter '" + name + "'");

@@ -3,6 +3,7 @@
 #include "physics.hpp"
 #include "linearelasticity.hpp"
 #include "cdr.hpp"
+#include "helmholtz.hpp"
 
 #include "expression.hpp"
 #include "porous_data.hpp"
@@ -554,6 +555,7 @@ std::unique_ptr<PhysicsBase> import_physics(int physics_id, int dim) {
   if (physics_id == MHA_PHYSICS_NAVIERSTOKES_THERMAL) return std::unique_ptr<PhysicsBase>(new navierstokesThermal(dim));
   if (physics_id == MHA_PHYSICS_LINEARELASTICITY) return std::unique_ptr<PhysicsBase>(new linearelasticity(dim));
   if (physics_id == MHA_PHYSICS_LINEARELASTICITY_THERMAL) return std::unique_ptr<PhysicsBase>(new linearelasticityThermal(dim));
+  if (physics_id == MHA_PHYSICS_HELMHOLTZ) return std::unique_ptr<PhysicsBase>(new helmholtz());
   if (physics_id == MHA_PHYSICS_CDR) return std::unique_ptr<PhysicsBase>(new cdr());
   if (physics_id == MHA_PHYSICS_NAVIERSTOKES_CDR) return std::unique_ptr<PhysicsBase>(new navierstokesCdr(dim));
   if (physics_id == MHA_PHYSICS_THERMAL) return std::unique_ptr<PhysicsBase>(new thermal());

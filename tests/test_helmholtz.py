@@ -1,0 +1,138 @@
+"""The yardstick of the helmholtz module, pinned without a GPU.
+
+tests/helmholtz_ref.py restates helmholtz::volumeResidual (src/physics/helmholtz.cpp:137-193) and ::boundaryResidual
+(:320-375) on the numpy forward-AD class, with vr and vi as separate arrays.  Here it is held against
+  * the reference's own gold regression/helmholtz/manufactured_solution (both printed values, as "%.6g" strings), on the
+    oracle's mesh with one direct sparse solve;
+  * a central difference of its own residual, volume and side terms: the form is linear in u, so the difference is exact
+    to rounding;
+  * the structure the issue names: every row couples to both variables, the operator is not symmetric, and the Robin
+    term's Jacobian holds the four N (grad N . n) blocks.
+Host-only checks of the module id follow.
+"""
+import os
+import re
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import helmholtz_ref as H
+from helmholtz_ref import rel_err
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden", "reference")
+
+
+def fmt(x):
+    return "%.6g" % x
+
+
+def gold_errors():
+    txt = open(os.path.join(GOLD, "helmholtz_manufactured.gold")).read()
+    return {k: float(v) for k, v in re.findall(r"L2 norm of the error for (\w+) = ([-0-9.e]+)", txt)}
+
+
+def constants(dim):
+    """every one of the ten volume functions and the four side-only ones non-zero and distinct"""
+    f = {"c2r_x": 1.3, "c2i_x": 0.35, "c2r_y": 0.9, "c2i_y": -0.45, "c2r_z": 1.1, "c2i_z": 0.25, "omega2r": 2.1,
+         "omega2i": -0.6, "source_r": 0.8, "source_i": -1.7, "robin_alpha_r": 0.55, "robin_alpha_i": -0.65,
+         "source_r_side": 1.9, "source_i_side": 0.75}
+    if dim == 2:
+        f.pop("c2r_z"), f.pop("c2i_z")
+    return f
+
+
+def test_gold_deck_is_the_mirrored_input():
+    """The function strings of the yardstick's gold driver are those of the mirrored input.yaml."""
+    txt = open(os.path.join(GOLD, "helmholtz_manufactured.input.yaml")).read()
+    deck = {k: v.strip().strip("'") for k, v in re.findall(r"^    (\w+): (.+)$", txt, re.M)
+            if k in H.GOLD_FUNCS}
+    assert deck == H.GOLD_FUNCS
+    assert re.search(r"NX: 100\s+NY: 100", txt) and "modules: helmholtz" in txt and "quadrature: 2" in txt
+
+
+def test_gold_manufactured(oracle):
+    def assemble(m, u, funcs, fixed, side):
+        ref = H.assemble(oracle, m, 2, u, funcs=funcs, fixed=fixed, sides=[side])
+        return H.with_identity_rows(ref, fixed, m["ndof"])
+    got = H.gold_manufactured(oracle, assemble)
+    g = gold_errors()
+    assert sorted(g) == ["uimag", "ureal"]
+    assert [fmt(v) for v in got] == [fmt(g["ureal"]), fmt(g["uimag"])] == ["0.000517267", "0.000222348"], (got, g)
+
+
+SHAPES = [(2, (3, 3), 1, 2), (2, (2, 2), 2, 4), (3, (2, 2, 2), 1, 2), (3, (2, 2, 1), 2, 4)]
+
+
+@pytest.mark.parametrize("dim,ncell,order,qdeg", SHAPES)
+@pytest.mark.parametrize("fset", ["constants", "gold"])
+def test_yardstick_jacobian_is_the_central_difference_of_its_residual(oracle, dim, ncell, order, qdeg, fset):
+    rng = np.random.default_rng(71)
+    m = H.helmholtz_mesh(oracle, dim, ncell, order)
+    funcs = constants(dim) if fset == "constants" else dict(H.GOLD_FUNCS, robin_alpha_r="0.3+x", robin_alpha_i="y-0.2")
+    sides = [H.all_sides_group(oracle, m)]
+    u = rng.uniform(-1, 1, m["ndof"])
+    a = H.assemble(oracle, m, qdeg, u, funcs=funcs, sides=sides)
+    J = H.dense(a, m["ndof"])
+    du = rng.uniform(-1, 1, m["ndof"])
+    p = H.assemble(oracle, m, qdeg, u + du, funcs=funcs, sides=sides)
+    q = H.assemble(oracle, m, qdeg, u - du, funcs=funcs, sides=sides)
+    lin = -(J @ du)  # the vector holds -res.val()
+    # linear form: the central difference with a step of order one is exact up to rounding
+    assert np.abs(0.5 * (p["res"] - q["res"]) - lin).max() < 1e-12 * np.abs(lin).max()
+
+
+@pytest.mark.parametrize("dim,ncell,order,qdeg", SHAPES[:1] + SHAPES[2:3])
+def test_structure_of_the_operator(oracle, dim, ncell, order, qdeg):
+    rng = np.random.default_rng(72)
+    m = H.helmholtz_mesh(oracle, dim, ncell, order)
+    u = rng.uniform(-1, 1, m["ndof"])
+    funcs = constants(dim)
+    vol = H.assemble(oracle, m, qdeg, u, funcs=funcs)
+    J = H.dense(vol, m["ndof"]).tocsr()
+    rows = [H.var_rows(m, v) for v in range(2)]
+    for a in range(2):
+        for b in range(2):  # every row of one variable couples to both
+            assert abs(J[rows[a]][:, rows[b]]).max() > 0.0
+    assert abs(J - J.T).max() > 1e-3 * abs(J).max()  # not symmetric
+    # defaults: all functions zero -> residual and matrix zero
+    z = H.assemble(oracle, m, qdeg, u)
+    assert np.all(z["res"] == 0.0) and np.all(z["crs_vals"] == 0.0)
+    # the Robin term with every function zero but nothing else: the four N (grad N . n) blocks alone
+    side = H.all_sides_group(oracle, m)
+    s = H.assemble_sides(oracle, m, qdeg, u, *side, rowptr=vol["rowptr"], colind=vol["colind"])
+    Js = H.dense(s, m["ndof"]).tocsr()
+    for a in range(2):
+        for b in range(2):
+            assert abs(Js[rows[a]][:, rows[b]]).max() > 0.0
+    # ... and they are sign-related as the form says: (ur, ur) = (ur, ui) = (ui, ui) = -(ui, ur)
+    D = Js.toarray()
+    blk = lambda a, b: D[np.ix_(rows[a], rows[b])]
+    assert rel_err(blk(0, 1), blk(0, 0)) < 1e-13 and rel_err(blk(1, 1), blk(0, 0)) < 1e-13
+    assert rel_err(-blk(1, 0), blk(0, 0)) < 1e-13
+
+
+def test_physics_id_agrees_with_the_header_and_the_keys_hold_two_digits():
+    import mrhyde_amd
+    src = open(os.path.join(ROOT, "include", "mrhyde_amd.h")).read()
+    last = int(re.search(r"#define\s+MHA_PHYSICS_LINEARELASTICITY_THERMAL\s+(\d+)", src).group(1))
+    mdef = re.search(r"#define\s+MHA_PHYSICS_HELMHOLTZ\s+\(MHA_PHYSICS_LINEARELASTICITY_THERMAL \+ (\d+)\)", src)
+    assert mdef and int(mdef.group(1)) == 3
+    ids = mrhyde_amd.api.ALL_PHYSICS_IDS
+    assert ids["helmholtz"] == mrhyde_amd.PHYSICS_HELMHOLTZ == last + 3 == 10
+    assert len(set(ids.values())) == len(ids)
+    for k, v in mrhyde_amd.api.PHYSICS_IDS.items():
+        assert ids[k] == v
+    # the four launchers key on dim * 100 + id
+    kdir = os.path.join(ROOT, "mrhyde_amd", "csrc", "kernels")
+    for name in ("point_engine.hip", "jacobian_apply.hip", "jacobian_apply_multi.hip", "jacobian_diagonal.hip"):
+        txt = open(os.path.join(kdir, name)).read()
+        assert "static_assert(MHA_PHYSICS_HELMHOLTZ < 100" in txt and "dim * 100 +" in txt and "dim * 10 +" not in txt, name
+        assert txt.count("MHA_PHYSICS_HELMHOLTZ") >= 3, name
+
+
+def test_select_without_a_context_is_refused():
+    import mrhyde_amd
+    lib = mrhyde_amd.load_library()
+    assert lib.mha_physics_select(None, mrhyde_amd.PHYSICS_HELMHOLTZ) != 0
