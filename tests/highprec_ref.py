@@ -2,7 +2,8 @@
 global CRS values and residuals in numpy's 80-bit longdouble / clongdouble (eps 1.08e-19) from 1-D ingredients that mpmath
 computes at 40 digits, and beside every entry the SCALE of its own sum, so that an entry is judged by its own condition.
 
-TEST INFRASTRUCTURE (the checker), imported by tests/test_highprec.py and tests/test_highprec_gpu.py only.  It shares no
+TEST INFRASTRUCTURE (the checker), imported by tests/test_highprec.py, tests/test_highprec_gpu.py and the HVOL/HDIV sibling
+tests/highprec_hdiv_ref.py only.  It shares no
 code, tables or derivative rules with oracle/ or mrhyde_amd/: quadrature and Lagrange tables come from mpmath, the
 geometry from the multilinear map of the element's vertices, the modules are restated as point functions from the
 reference's loop nests, and their derivatives are complex steps (no hand-written derivative, no AD rules).
