@@ -1,7 +1,11 @@
-// engine_points.hpp -- what the kernels that run the modules' point functions share (point_engine.hip: element matrix
-// and residual; jacobian_apply.hip: matrix-free products with the same Jacobian): the static variable layout of every
-// module, the geometric block G between reference and physical slots, the geometry of an integration point, and the
-// dispatch to the point functions of physics_points.hpp.
+// engine_points.hpp -- the device side that the kernels running the modules' point functions share (point_engine.hip:
+// element matrix and residual; jacobian_apply.hip, jacobian_apply_multi.hip: matrix-free products with the same
+// Jacobian; jacobian_diagonal.hip: its diagonal): the static variable layout of every module, the geometric block G
+// between reference and physical slots, the geometry of an integration point, the dispatch to the point functions of
+// physics_points.hpp, and -- as macros, see below -- the statements the four element loops have in common: var_at, the
+// element range of a wave, the dof gather's row and sign, the reference-slot fields, the element size, the phase-3
+// seeding, the point function's arguments and the back-transform.  The host side of the same kernels is
+// engine_dispatch.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -187,6 +191,114 @@ constexpr int geo_size() { return 2 * DIM * DIM + 2 + DIM; }  // J, Ji, det, w, 
 
 }  // namespace
 }  // namespace mha
+
+// ---- statements the four kernels share, as text ----
+// Macros, not functions, and with the index expressions the kernels had (s_Uh[q * NS + sp + sl], not a pointer advanced
+// to the point first): moved into an inlined function template the seeding loop changed the resource usage of 17 of
+// jacobian_diagonal.hip's kernels; as these macros every kernel of the four files compiles to the instructions it had
+// before they were shared.  Each names what it needs in scope; all need L, DIM and NS.
+
+// layout of the variable that holds slot m / dof f: declares VarAt and var_at(key, by_slot).  The loop runs over the
+// module's compile-time variable count, so the layout arrays are indexed statically (kernel arguments in scalar
+// registers); indexed by a run-time variable number they are memory loads, one dependent on the other, in every phase
+// of every element.  Needs vl.
+#define MHA_VAR_AT()                                                                                                     \
+  struct VarAt { int sp, nsl, card, cp, vp, to; };                                                                       \
+  auto var_at = [&](int key, bool by_slot) {                                                                             \
+    VarAt r = {vl.slotptr[0], vl.nslot[0], vl.card[0], vl.cardpad[0], vl.varptr[0], vl.table_off[0]};                    \
+    _Pragma("unroll") for (int k = 1; k < L::nvars; ++k)                                                                 \
+      if (key >= (by_slot ? vl.slotptr[k] : vl.varptr[k]))                                                               \
+        r = {vl.slotptr[k], vl.nslot[k], vl.card[k], vl.cardpad[k], vl.varptr[k], vl.table_off[k]};                      \
+    return r;                                                                                                            \
+  }
+
+// blocked element ranges per wave (wave `wave` of NW in the workgroup): waves running at the same time work far apart
+// in the mesh.  Declares el_begin, el_end.  Needs b.
+#define MHA_WAVE_ELEMENT_RANGE(NW, wave)                                                                                 \
+  const int nwaves = gridDim.x * (NW), gid = blockIdx.x * (NW) + (wave);                                                 \
+  const int chunk = (b.e_count + nwaves - 1) / nwaves;                                                                   \
+  const int el_begin = gid * chunk, el_end = min(b.e_count, el_begin + chunk)
+
+// dof f of element e: declares pos, row and the orientation sign sg.  Needs b, vl, e, n.
+#define MHA_DOF_ROW(f)                                                                                                   \
+  const int pos = b.offsets[f], row = b.lids[(size_t)e * n + pos];                                                       \
+  const double sg = vl.orient ? (double)vl.orient[(size_t)e * n + f] : 1.0
+
+// work item idx = (point q, slot m) of phase 2: declares q, m, va, sl, card and T, the table row of (q, m).  Needs tab,
+// var_at.
+#define MHA_REF_SLOT(idx)                                                                                                \
+  const int q = (idx) / NS, m = (idx) - q * NS;                                                                          \
+  const VarAt va = var_at(m, true);                                                                                      \
+  const int sl = m - va.sp, card = va.card;                                                                              \
+  const double *T = tab + va.to + (q * va.nsl + sl) * va.cp
+
+// U^(q,m), Udot^(q,m) of the item MHA_REF_SLOT(idx) opened.  Needs s_u, s_ud, s_Uh, s_Udh, tm.
+#define MHA_REF_FIELDS(idx)                                                                                              \
+  do {                                                                                                                   \
+    const double *uu = s_u + va.vp, *ud = s_ud + va.vp;                                                                  \
+    double a = 0.0, ad = 0.0;                                                                                            \
+    if (tm.transient) {                                                                                                  \
+      _Pragma("unroll 4") for (int dof = 0; dof < card; ++dof) {                                                         \
+        a += uu[dof] * T[dof];                                                                                           \
+        ad += ud[dof] * T[dof];                                                                                          \
+      }                                                                                                                  \
+    } else { /* steady: the time-derivative coefficients are zero */                                                     \
+      _Pragma("unroll 4") for (int dof = 0; dof < card; ++dof) a += uu[dof] * T[dof];                                    \
+    }                                                                                                                    \
+    s_Uh[idx] = a;                                                                                                       \
+    s_Udh[idx] = ad;                                                                                                     \
+  } while (0)
+
+// element size: declares h.  Workset::getElementSize (workset.cpp:2666-2679).  Needs s_geo, NQ, GEO.
+#define MHA_ELEMENT_SIZE()                                                                                               \
+  double vol = 0.0;                                                                                                      \
+  for (int q = 0; q < NQ; ++q) vol += s_geo[q * GEO + 2 * DIM * DIM + 1];                                                \
+  const double h = (DIM == 2) ? sqrt(vol) : cbrt(vol)
+
+// geometry of point q as phase 3 reads it: declares g, J, Ji, det, w.  Needs s_geo, GEO, q.
+#define MHA_POINT_GEO()                                                                                                  \
+  const double *g = s_geo + q * GEO;                                                                                     \
+  const double *J = g, *Ji = g + DIM * DIM;                                                                              \
+  const double det = g[2 * DIM * DIM], w = g[2 * DIM * DIM + 1]
+
+// seeding of phase 3: fills U, Ud (Dual[NS], in scope) with the physical fields at point q, derivative parts along the
+// direction whose reference slot sp + sl is DIR -- an expression in q, m, sp, sl (the unit direction m:
+// (m == sp + sl) ? 1.0 : 0.0).
+// Needs s_Uh, s_Udh, q, tm and MHA_POINT_GEO.
+#define MHA_SEED_POINT(DIR)                                                                                              \
+  _Pragma("unroll") for (int v = 0; v < L::nvars; ++v) {                                                                 \
+    const int type = L::type(v), sp = slotptr_of<L, DIM>(v), ns = slots_of(type, DIM);                                   \
+    double ref[1 + DIM], phys[1 + DIM], refd[1 + DIM], physd[1 + DIM], dir[1 + DIM], pdir[1 + DIM];                      \
+    _Pragma("unroll") for (int sl = 0; sl < ns; ++sl) {                                                                  \
+      ref[sl] = s_Uh[q * NS + sp + sl];                                                                                  \
+      refd[sl] = s_Udh[q * NS + sp + sl];                                                                                \
+      dir[sl] = DIR;                                                                                                     \
+    }                                                                                                                    \
+    to_phys<DIM>(type, ref, J, Ji, det, phys);                                                                           \
+    to_phys<DIM>(type, refd, J, Ji, det, physd);                                                                         \
+    to_phys<DIM>(type, dir, J, Ji, det, pdir);                                                                           \
+    _Pragma("unroll") for (int sl = 0; sl < ns; ++sl) {                                                                  \
+      U[sp + sl] = mk(phys[sl], tm.alpha_u * pdir[sl]);                                                                  \
+      Ud[sp + sl] = value_like(type, sl, DIM) ? mk(physd[sl], tm.alpha_t * pdir[sl]) : mk(0.0);                          \
+    }                                                                                                                    \
+  }
+
+// declares pa, the point function's arguments at point q of element e.  Needs U, Ud, g, h, tm, e, q, NQ, pp.
+#define MHA_POINT_ARGS(pa)                                                                                               \
+  PointArgs<DIM> pa;                                                                                                     \
+  pa.U = U; pa.Ud = Ud; pa.x = g + 2 * DIM * DIM + 2; pa.h = h; pa.dt = tm.dt;                                           \
+  pa.transient = tm.transient; pa.e = e; pa.q = q; pa.nq = NQ; pa.pp = &pp
+
+// back-transform w G^T F.d, variable by variable: STORE is a statement that takes w * ref[sl], the coefficient of
+// reference slot sp + sl.  Needs MHA_POINT_GEO.
+#define MHA_BACK_TRANSFORM(F, STORE)                                                                                     \
+  _Pragma("unroll") for (int v = 0; v < L::nvars; ++v) {                                                                 \
+    const int type = L::type(v), sp = slotptr_of<L, DIM>(v), ns = slots_of(type, DIM);                                   \
+    double phys[1 + DIM], ref[1 + DIM];                                                                                  \
+    _Pragma("unroll") for (int sl = 0; sl < ns; ++sl) phys[sl] = F[sp + sl].d;                                           \
+    to_ref_T<DIM>(type, phys, J, Ji, det, ref);                                                                          \
+    _Pragma("unroll") for (int sl = 0; sl < ns; ++sl) { STORE; }                                                         \
+  }
 
 // the module's point function.  EXPR: 0 / 1 deck strings / 2 deck strings that read the solution fields (thermal, cdr,
 // navierstokes+cdr) / 3 porousMixed with heterogeneous permeability (no deck strings).  A macro for the same reason as

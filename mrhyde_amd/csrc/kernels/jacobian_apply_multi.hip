@@ -8,27 +8,26 @@
 //   transposed  work items (point, unit direction m) as in the single product: one evaluation, then Kc contractions
 //               z^_k(q,m) = sum_s C^_sm X^_k(q,s) in the thread
 //   phase 4     work items (dof, vector), atomics into Y_k
-// Kc is a kernel argument, not a template parameter: the instantiations are the single product's 84.  The launcher
+// Kc is a kernel argument, not a template parameter: the instantiations are the single product's 92.  The launcher
 // takes nvec vectors in passes of Kc <= MHA_APPLY_MAX_VECTORS and chooses Kc per shape (choose_vectors); a pass of one
 // vector runs jacobian_apply.hip's kernel.
 //
 // Layout as in jacobian_apply.hip: one wavefront per element, wave-level synchronisation only, waves persistent over
-// blocked element ranges.  Self-contained: the statements shared with jacobian_apply.hip are repeated here rather
-// than moved to a header, so that file's kernels stay what they were.
+// blocked element ranges.  The statements the element loop has in common with the other point-function kernels are
+// engine_points.hpp's macros, the launcher's checks and choices engine_dispatch.hpp's; the handling of
+// x_k is this file's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <type_traits>
 
 #include "device_math.hpp"
+#include "engine_dispatch.hpp"
 #include "engine_points.hpp"
 #include "launch.hpp"
 
 namespace mha {
 namespace {
-
-constexpr int kMultiMaxWaves = 8;
-constexpr size_t kMultiLdsLimit = 160 * 1024;
 
 // per-element LDS (doubles): u, udot, sign, x_k | geometry | U^, Udot^, X^_k, F^x_k or z^_k | row (ints)
 __host__ __device__ inline size_t multi_wave_doubles(const VarLayoutDev &vl, int geo, int kc) {
@@ -37,7 +36,7 @@ __host__ __device__ inline size_t multi_wave_doubles(const VarLayoutDev &vl, int
 }
 
 template <int DIM, int PHYS, int EXPR, int TRANSPOSE>
-__global__ __launch_bounds__(64 * kMultiMaxWaves) void jacobian_apply_multi_kernel(
+__global__ __launch_bounds__(64 * kProductMaxWaves) void jacobian_apply_multi_kernel(
     BlockDev b, VarLayoutDev vl, PhysParamsDev pp, TimeDev tm, int Kc, const double *__restrict__ x, int64_t ldx,
     double *__restrict__ y, int64_t ldy) {
   using L = Layout<PHYS, DIM>;
@@ -55,27 +54,14 @@ __global__ __launch_bounds__(64 * kMultiMaxWaves) void jacobian_apply_multi_kern
   for (int k = tid; k < vl.tables_size; k += blockDim.x) tab[k] = vl.tables[k];
   __syncthreads();  // the only workgroup barrier: from here on a wave meets nobody
 
-  // blocked element ranges per wave: waves running at the same time work far apart in the mesh
-  const int nwaves = gridDim.x * NW, gid = blockIdx.x * NW + wave;
-  const int chunk = (b.e_count + nwaves - 1) / nwaves;
-  const int el_begin = gid * chunk, el_end = min(b.e_count, el_begin + chunk);
-  // layout of the variable that holds slot m / dof f (compile-time variable count: see point_engine.hip)
-  struct VarAt { int sp, nsl, card, cp, vp, to; };
-  auto var_at = [&](int key, bool by_slot) {
-    VarAt r = {vl.slotptr[0], vl.nslot[0], vl.card[0], vl.cardpad[0], vl.varptr[0], vl.table_off[0]};
-#pragma unroll
-    for (int k = 1; k < L::nvars; ++k)
-      if (key >= (by_slot ? vl.slotptr[k] : vl.varptr[k]))
-        r = {vl.slotptr[k], vl.nslot[k], vl.card[k], vl.cardpad[k], vl.varptr[k], vl.table_off[k]};
-    return r;
-  };
+  MHA_WAVE_ELEMENT_RANGE(NW, wave);
+  MHA_VAR_AT();
   for (int el = el_begin; el < el_end; ++el) {
     const int e = b.e_begin + el;
     wave_lds_sync();  // previous element done with the wave's LDS
     // ---- 1. gather u + seeding values once, x_k (x orientation sign) per vector, geometry ----
     for (int f = lane; f < n; f += 64) {
-      const int pos = b.offsets[f], row = b.lids[(size_t)e * n + pos];
-      const double sg = vl.orient ? (double)vl.orient[(size_t)e * n + f] : 1.0;
+      MHA_DOF_ROW(f);
       double ue, ud;
       stage_state(tm, row, tm.u[row], ue, ud);
       const bool zero = TRANSPOSE && b.fixed && b.fixed[row];  // A has no entries in that row
@@ -90,25 +76,9 @@ __global__ __launch_bounds__(64 * kMultiMaxWaves) void jacobian_apply_multi_kern
     // ---- 2. reference-slot fields: items (point, slot, field), field 0 = u and udot, field 1 + k = x_k ----
     for (int item = lane; item < QS * (1 + Kc); item += 64) {
       const int t = item / QS, idx = item - t * QS;
-      const int q = idx / NS, m = idx - q * NS;
-      const VarAt va = var_at(m, true);
-      const int sl = m - va.sp, card = va.card;
-      const double *T = tab + va.to + (q * va.nsl + sl) * va.cp;
+      MHA_REF_SLOT(idx);
       if (t == 0) {
-        const double *uu = s_u + va.vp, *ud = s_ud + va.vp;
-        double a = 0.0, ad = 0.0;
-        if (tm.transient) {
-#pragma unroll 4
-          for (int dof = 0; dof < card; ++dof) {
-            a += uu[dof] * T[dof];
-            ad += ud[dof] * T[dof];
-          }
-        } else {  // steady: the time-derivative coefficients are zero
-#pragma unroll 4
-          for (int dof = 0; dof < card; ++dof) a += uu[dof] * T[dof];
-        }
-        s_Uh[idx] = a;
-        s_Udh[idx] = ad;
+        MHA_REF_FIELDS(idx);
       } else {
         const double *xx = s_x + (t - 1) * n + va.vp;
         double ax = 0.0;
@@ -119,51 +89,18 @@ __global__ __launch_bounds__(64 * kMultiMaxWaves) void jacobian_apply_multi_kern
     }
     wave_lds_sync();
     // ---- 3. point function: forward items (point, vector), direction G X^_k; transposed items (point, direction) ----
-    double vol = 0.0;
-    for (int q = 0; q < NQ; ++q) vol += s_geo[q * GEO + 2 * DIM * DIM + 1];
-    const double h = (DIM == 2) ? sqrt(vol) : cbrt(vol);  // Workset::getElementSize (workset.cpp:2666-2679)
+    MHA_ELEMENT_SIZE();
     for (int idx = lane; idx < (TRANSPOSE ? QS : NQ * Kc); idx += 64) {
       const int kv = TRANSPOSE ? 0 : idx / NQ;  // forward: the item's vector
       const int q = TRANSPOSE ? idx / NS : idx - kv * NQ, m = TRANSPOSE ? idx - q * NS : 0;
-      const double *g = s_geo + q * GEO;
-      const double *J = g, *Ji = g + DIM * DIM;
-      const double det = g[2 * DIM * DIM], w = g[2 * DIM * DIM + 1];
+      MHA_POINT_GEO();
       const double *Xk = s_Xh + kv * QS + q * NS;
       Dual U[NS], Ud[NS], F[NS];
-#pragma unroll
-      for (int v = 0; v < L::nvars; ++v) {
-        const int type = L::type(v), sp = slotptr_of<L, DIM>(v), ns = slots_of(type, DIM);
-        double ref[1 + DIM], phys[1 + DIM], refd[1 + DIM], physd[1 + DIM], dir[1 + DIM], pdir[1 + DIM];
-#pragma unroll
-        for (int sl = 0; sl < ns; ++sl) {
-          ref[sl] = s_Uh[q * NS + sp + sl];
-          refd[sl] = s_Udh[q * NS + sp + sl];
-          dir[sl] = TRANSPOSE ? ((m == sp + sl) ? 1.0 : 0.0) : Xk[sp + sl];
-        }
-        to_phys<DIM>(type, ref, J, Ji, det, phys);
-        to_phys<DIM>(type, refd, J, Ji, det, physd);
-        to_phys<DIM>(type, dir, J, Ji, det, pdir);
-#pragma unroll
-        for (int sl = 0; sl < ns; ++sl) {
-          U[sp + sl] = mk(phys[sl], tm.alpha_u * pdir[sl]);
-          Ud[sp + sl] = value_like(type, sl, DIM) ? mk(physd[sl], tm.alpha_t * pdir[sl]) : mk(0.0);
-        }
-      }
-      PointArgs<DIM> pa;
-      pa.U = U; pa.Ud = Ud; pa.x = g + 2 * DIM * DIM + 2; pa.h = h; pa.dt = tm.dt;
-      pa.transient = tm.transient; pa.e = e; pa.q = q; pa.nq = NQ; pa.pp = &pp;
+      MHA_SEED_POINT(TRANSPOSE ? ((m == sp + sl) ? 1.0 : 0.0) : Xk[sp + sl]);
+      MHA_POINT_ARGS(pa);
       MHA_MODULE_POINT(pa, F);
       double col[NS];  // w G^T F.d: forward F^x_k(q), transposed column m of C^(q)
-#pragma unroll
-      for (int v = 0; v < L::nvars; ++v) {
-        const int type = L::type(v), sp = slotptr_of<L, DIM>(v), ns = slots_of(type, DIM);
-        double phys[1 + DIM], ref[1 + DIM];
-#pragma unroll
-        for (int sl = 0; sl < ns; ++sl) phys[sl] = F[sp + sl].d;
-        to_ref_T<DIM>(type, phys, J, Ji, det, ref);
-#pragma unroll
-        for (int sl = 0; sl < ns; ++sl) col[sp + sl] = w * ref[sl];
-      }
+      MHA_BACK_TRANSFORM(F, col[sp + sl] = w * ref[sl]);
       if (TRANSPOSE) {
         for (int k = 0; k < Kc; ++k) {
           const double *xh = s_Xh + k * QS + q * NS;
@@ -214,9 +151,7 @@ __global__ __launch_bounds__(64 * kMultiMaxWaves) void jacobian_apply_multi_kern
 constexpr int kMultiMinWaves = 7;
 
 inline int waves_for(const VarLayoutDev &vl, int geo, size_t tables, int kc) {
-  const size_t per_wave = multi_wave_doubles(vl, geo, kc) * sizeof(double);
-  if (tables + per_wave > kMultiLdsLimit) return 0;
-  return static_cast<int>(std::min<size_t>(kMultiMaxWaves, (kMultiLdsLimit - tables) / per_wave));
+  return waves_that_fit(tables, multi_wave_doubles(vl, geo, kc) * sizeof(double));
 }
 
 inline int choose_vectors(const VarLayoutDev &vl, int geo, size_t tables, int nvec) {
@@ -230,33 +165,19 @@ template <int DIM, int PHYS>
 void launch_typed(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp, const TimeDev &tm, int nvec,
                   const double *x, int64_t ldx, double *y, int64_t ldy, int transpose, int overwrite, hipStream_t stream,
                   size_t *lds_bytes, int *waves, int *vectors) {
-  using L = Layout<PHYS, DIM>;
-  MHA_REQUIRE(vl.nvars == L::nvars && vl.ns_tot == L::NS, MHA_ERR_INVALID,
-              "variable layout does not match the physics module (" << vl.nvars << " variables, " << vl.ns_tot
-                                                                    << " slots)");
-  for (int v = 0; v < L::nvars; ++v)
-    MHA_REQUIRE(vl.type[v] == L::type(v), MHA_ERR_INVALID, "basis type of variable " << v << " does not match the module");
+  require_layout<PHYS, DIM>(vl);
   const size_t tables = vl.tables_size * sizeof(double);
-  MHA_REQUIRE(waves_for(vl, geo_size<DIM>(), tables, 1) >= 1, MHA_ERR_INVALID,
-              "element needs " << tables + multi_wave_doubles(vl, geo_size<DIM>(), 1) * sizeof(double)
-                               << " B of LDS (limit 160 KB)");
+  require_wave_fits(tables, multi_wave_doubles(vl, geo_size<DIM>(), 1) * sizeof(double));
   const int kc_max = choose_vectors(vl, geo_size<DIM>(), tables, nvec);
-  const int num_cu = current_device_num_cus();
   auto go = [&](auto kern) {
-    require_modest_scratch(kern, "Jacobian product");
-    MHA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(kMultiLdsLimit)));
+    prepare_kernel(kern, "Jacobian product");
     // passes of kc_max vectors and a remainder; each pass sized for its own Kc and zeroing its own vectors first
     for (int k0 = 0; k0 < nvec; k0 += kc_max) {
       const int kc = std::min(kc_max, nvec - k0);
-      const size_t per_wave = multi_wave_doubles(vl, geo_size<DIM>(), kc) * sizeof(double);
-      const int nw = waves_for(vl, geo_size<DIM>(), tables, kc);
-      const size_t lds = tables + nw * per_wave;
-      const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(size_t(4), kMultiLdsLimit / lds)));
-      const int grid = std::max(1, std::min((b.e_count + nw - 1) / nw, num_cu * per_cu));
+      const WaveLaunch g = wave_launch(tables, multi_wave_doubles(vl, geo_size<DIM>(), kc) * sizeof(double), b.e_count);
       if (k0 == 0) {  // reported: the first (full) pass
-        if (lds_bytes) *lds_bytes = lds;
-        if (waves) *waves = nw;
+        if (lds_bytes) *lds_bytes = g.lds;
+        if (waves) *waves = g.nw;
         if (vectors) *vectors = kc;
       }
       if (kc == 1) {  // the single product's launch: same checks, same dispatch, same memset
@@ -265,34 +186,16 @@ void launch_typed(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev
       }
       if (overwrite)  // the vectors, not the padding between them
         MHA_HIP(hipMemset2DAsync(y + k0 * ldy, sizeof(double) * ldy, 0, sizeof(double) * b.nrows, kc, stream));
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, stream, b, vl, pp, tm, kc, x + k0 * ldx, ldx, y + k0 * ldy,
-                         ldy);
+      hipLaunchKernelGGL(kern, dim3(g.grid), dim3(64 * g.nw), g.lds, stream, b, vl, pp, tm, kc, x + k0 * ldx, ldx,
+                         y + k0 * ldy, ldy);
       MHA_HIP(hipGetLastError());
     }
   };
-  auto pick = [&](auto expr) {
+  dispatch_expr<PHYS>(pp, [&](auto expr) {
     constexpr int E = decltype(expr)::value;
     if (transpose) go(jacobian_apply_multi_kernel<DIM, PHYS, E, 1>);
     else go(jacobian_apply_multi_kernel<DIM, PHYS, E, 0>);
-  };
-  if (uses_fields(pp)) {
-    // deck strings that read the solution fields: built for the modules whose point function has an EXPR = 2 form
-    if constexpr (PHYS == MHA_PHYSICS_THERMAL || PHYS == MHA_PHYSICS_CDR || PHYS == MHA_PHYSICS_NAVIERSTOKES_CDR) {
-      pick(std::integral_constant<int, 2>());
-    } else {
-      MHA_REQUIRE(false, MHA_ERR_INVALID, "functions of the solution fields are built for the thermal module");
-    }
-  } else if (PHYS == MHA_PHYSICS_POROUS_MIXED && (pp.het.edata || pp.het.kl)) {
-    if constexpr (PHYS == MHA_PHYSICS_POROUS_MIXED) {
-      MHA_REQUIRE(!has_expression(pp), MHA_ERR_INVALID,
-                  "porousMixed: heterogeneous permeability with deck-string functions is not built; give source / mobility as constants or closed forms");
-      pick(std::integral_constant<int, 3>());
-    }
-  } else if (has_expression(pp)) {
-    pick(std::integral_constant<int, 1>());
-  } else {
-    pick(std::integral_constant<int, 0>());
-  }
+  });
 }
 
 }  // namespace
@@ -309,34 +212,10 @@ void launch_jacobian_apply_multi(const BlockDev &b, const VarLayoutDev &vl, cons
     if (overwrite) MHA_HIP(hipMemset2DAsync(y, sizeof(double) * ldy, 0, sizeof(double) * b.nrows, nvec, stream));
     return;
   }
-  static_assert(MHA_PHYSICS_HELMHOLTZ < 100, "the switch key holds two decimal digits of module id");
-#define MHA_APPLY_CASE(D, P)                                                                                              \
-  case D * 100 + P:                                                                                                       \
-    launch_typed<D, P>(b, vl, pp, tm, nvec, x, ldx, y, ldy, transpose, overwrite, stream, lds_bytes, waves, vectors);     \
-    break;
-  switch (b.dim * 100 + pp.physics) {
-    MHA_APPLY_CASE(2, MHA_PHYSICS_THERMAL)
-    MHA_APPLY_CASE(3, MHA_PHYSICS_THERMAL)
-    MHA_APPLY_CASE(2, MHA_PHYSICS_POROUS_MIXED)
-    MHA_APPLY_CASE(3, MHA_PHYSICS_POROUS_MIXED)
-    MHA_APPLY_CASE(2, MHA_PHYSICS_NAVIERSTOKES)
-    MHA_APPLY_CASE(3, MHA_PHYSICS_NAVIERSTOKES)
-    MHA_APPLY_CASE(2, MHA_PHYSICS_NAVIERSTOKES_THERMAL)
-    MHA_APPLY_CASE(3, MHA_PHYSICS_NAVIERSTOKES_THERMAL)
-    MHA_APPLY_CASE(2, MHA_PHYSICS_LINEARELASTICITY)
-    MHA_APPLY_CASE(3, MHA_PHYSICS_LINEARELASTICITY)
-    MHA_APPLY_CASE(2, MHA_PHYSICS_LINEARELASTICITY_THERMAL)
-    MHA_APPLY_CASE(3, MHA_PHYSICS_LINEARELASTICITY_THERMAL)
-    MHA_APPLY_CASE(2, MHA_PHYSICS_CDR)
-    MHA_APPLY_CASE(3, MHA_PHYSICS_CDR)
-    MHA_APPLY_CASE(2, MHA_PHYSICS_NAVIERSTOKES_CDR)
-    MHA_APPLY_CASE(3, MHA_PHYSICS_NAVIERSTOKES_CDR)
-    MHA_APPLY_CASE(2, MHA_PHYSICS_HELMHOLTZ)
-    MHA_APPLY_CASE(3, MHA_PHYSICS_HELMHOLTZ)
-    MHA_APPLY_CASE(2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED)
-    default: MHA_REQUIRE(false, MHA_ERR_INVALID, "no Jacobian-product kernel for physics " << pp.physics << " in " << b.dim << "-D");
-  }
-#undef MHA_APPLY_CASE
+  dispatch_module(b.dim, pp.physics, "Jacobian-product", [&](auto dim, auto phys) {
+    launch_typed<decltype(dim)::value, decltype(phys)::value>(b, vl, pp, tm, nvec, x, ldx, y, ldy, transpose, overwrite,
+                                                              stream, lds_bytes, waves, vectors);
+  });
 }
 
 }  // namespace mha

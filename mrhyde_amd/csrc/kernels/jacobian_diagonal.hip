@@ -9,22 +9,22 @@
 //
 // Layout as in jacobian_apply.hip: one wavefront per element, wave-level synchronisation only, as many wavefronts per
 // workgroup as the LDS holds beside the tables, waves persistent over blocked element ranges, d written with atomics.
-// Self-contained: phases 1-2 and the seeding repeat jacobian_apply.hip's statements rather than share them through
-// a header, so that file's kernels stay what they were.
+// The statements the element loop has in common with the other point-function kernels are engine_points.hpp's macros,
+// the launcher's checks and choices engine_dispatch.hpp's.  Its own: var_at with the offset `co` of the
+// variable's block of C^ (beside the shared one the offset cost other SGPR spill counts), and the back-transform, which
+// runs for the variable of m alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <type_traits>
 
 #include "device_math.hpp"
+#include "engine_dispatch.hpp"
 #include "engine_points.hpp"
 #include "launch.hpp"
 
 namespace mha {
 namespace {
-
-constexpr int kDiagMaxWaves = 8;
-constexpr size_t kDiagLdsLimit = 160 * 1024;
 
 // sum_v ns_v^2: the doubles of the kept blocks of C^ at one point
 template <class L, int DIM>
@@ -42,7 +42,7 @@ __host__ __device__ inline size_t diag_wave_doubles(const VarLayoutDev &vl, int 
 }
 
 template <int DIM, int PHYS, int EXPR>
-__global__ __launch_bounds__(64 * kDiagMaxWaves) void jacobian_diagonal_kernel(BlockDev b, VarLayoutDev vl, PhysParamsDev pp,
+__global__ __launch_bounds__(64 * kProductMaxWaves) void jacobian_diagonal_kernel(BlockDev b, VarLayoutDev vl, PhysParamsDev pp,
                                                                                TimeDev tm, double *__restrict__ d) {
   using L = Layout<PHYS, DIM>;
   constexpr int NS = L::NS, GEO = geo_size<DIM>(), CS = coupling_size<L, DIM>();
@@ -58,9 +58,7 @@ __global__ __launch_bounds__(64 * kDiagMaxWaves) void jacobian_diagonal_kernel(B
   for (int k = tid; k < vl.tables_size; k += blockDim.x) tab[k] = vl.tables[k];
   __syncthreads();  // the only workgroup barrier: from here on a wave meets nobody
 
-  const int nwaves = gridDim.x * NW, gid = blockIdx.x * NW + wave;
-  const int chunk = (b.e_count + nwaves - 1) / nwaves;
-  const int el_begin = gid * chunk, el_end = min(b.e_count, el_begin + chunk);
+  MHA_WAVE_ELEMENT_RANGE(NW, wave);
   // layout of the variable that holds slot m / dof f; co: offset of its block of C^
   struct VarAt { int sp, nsl, card, cp, vp, to, co; };
   auto var_at = [&](int key, bool by_slot) {
@@ -76,8 +74,7 @@ __global__ __launch_bounds__(64 * kDiagMaxWaves) void jacobian_diagonal_kernel(B
     wave_lds_sync();  // previous element done with the wave's LDS
     // ---- 1. gather u + seeding values, geometry ----
     for (int f = lane; f < n; f += 64) {
-      const int pos = b.offsets[f], row = b.lids[(size_t)e * n + pos];
-      const double sg = vl.orient ? (double)vl.orient[(size_t)e * n + f] : 1.0;
+      MHA_DOF_ROW(f);
       double ue, ud;
       stage_state(tm, row, tm.u[row], ue, ud);
       s_u[f] = ue * sg;
@@ -88,59 +85,20 @@ __global__ __launch_bounds__(64 * kDiagMaxWaves) void jacobian_diagonal_kernel(B
     wave_lds_sync();
     // ---- 2. reference-slot fields of u and udot ----
     for (int idx = lane; idx < NQ * NS; idx += 64) {
-      const int q = idx / NS, m = idx - q * NS;
-      const VarAt va = var_at(m, true);
-      const int sl = m - va.sp, card = va.card;
-      const double *T = tab + va.to + (q * va.nsl + sl) * va.cp;
-      const double *uu = s_u + va.vp, *ud = s_ud + va.vp;
-      double a = 0.0, ad = 0.0;
-      if (tm.transient) {
-#pragma unroll 4
-        for (int dof = 0; dof < card; ++dof) {
-          a += uu[dof] * T[dof];
-          ad += ud[dof] * T[dof];
-        }
-      } else {  // steady: the time-derivative coefficients are zero
-#pragma unroll 4
-        for (int dof = 0; dof < card; ++dof) a += uu[dof] * T[dof];
-      }
-      s_Uh[idx] = a;
-      s_Udh[idx] = ad;
+      MHA_REF_SLOT(idx);
+      MHA_REF_FIELDS(idx);
     }
     wave_lds_sync();
     // ---- 3. point function, one thread per (point, unit direction m): column m of C^(q), rows of m's variable ----
-    double vol = 0.0;
-    for (int q = 0; q < NQ; ++q) vol += s_geo[q * GEO + 2 * DIM * DIM + 1];
-    const double h = (DIM == 2) ? sqrt(vol) : cbrt(vol);  // Workset::getElementSize (workset.cpp:2666-2679)
+    MHA_ELEMENT_SIZE();
     for (int idx = lane; idx < NQ * NS; idx += 64) {
       const int q = idx / NS, m = idx - q * NS;
-      const double *g = s_geo + q * GEO;
-      const double *J = g, *Ji = g + DIM * DIM;
-      const double det = g[2 * DIM * DIM], w = g[2 * DIM * DIM + 1];
+      MHA_POINT_GEO();
       Dual U[NS], Ud[NS], F[NS];
-#pragma unroll
-      for (int v = 0; v < L::nvars; ++v) {
-        const int type = L::type(v), sp = slotptr_of<L, DIM>(v), ns = slots_of(type, DIM);
-        double ref[1 + DIM], phys[1 + DIM], refd[1 + DIM], physd[1 + DIM], dir[1 + DIM], pdir[1 + DIM];
-#pragma unroll
-        for (int sl = 0; sl < ns; ++sl) {
-          ref[sl] = s_Uh[q * NS + sp + sl];
-          refd[sl] = s_Udh[q * NS + sp + sl];
-          dir[sl] = (m == sp + sl) ? 1.0 : 0.0;
-        }
-        to_phys<DIM>(type, ref, J, Ji, det, phys);
-        to_phys<DIM>(type, refd, J, Ji, det, physd);
-        to_phys<DIM>(type, dir, J, Ji, det, pdir);
-#pragma unroll
-        for (int sl = 0; sl < ns; ++sl) {
-          U[sp + sl] = mk(phys[sl], tm.alpha_u * pdir[sl]);
-          Ud[sp + sl] = value_like(type, sl, DIM) ? mk(physd[sl], tm.alpha_t * pdir[sl]) : mk(0.0);
-        }
-      }
-      PointArgs<DIM> pa;
-      pa.U = U; pa.Ud = Ud; pa.x = g + 2 * DIM * DIM + 2; pa.h = h; pa.dt = tm.dt;
-      pa.transient = tm.transient; pa.e = e; pa.q = q; pa.nq = NQ; pa.pp = &pp;
+      MHA_SEED_POINT((m == sp + sl) ? 1.0 : 0.0);
+      MHA_POINT_ARGS(pa);
       MHA_MODULE_POINT(pa, F);
+      // the back-transform is not MHA_BACK_TRANSFORM: it runs for the variable of m alone
 #pragma unroll
       for (int v = 0; v < L::nvars; ++v) {
         const int type = L::type(v), sp = slotptr_of<L, DIM>(v), ns = slots_of(type, DIM);
@@ -189,49 +147,18 @@ template <int DIM, int PHYS>
 void launch_typed(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp, const TimeDev &tm, double *d,
                   int overwrite, hipStream_t stream, size_t *lds_bytes, int *waves) {
   using L = Layout<PHYS, DIM>;
-  MHA_REQUIRE(vl.nvars == L::nvars && vl.ns_tot == L::NS, MHA_ERR_INVALID,
-              "variable layout does not match the physics module (" << vl.nvars << " variables, " << vl.ns_tot
-                                                                    << " slots)");
-  for (int v = 0; v < L::nvars; ++v)
-    MHA_REQUIRE(vl.type[v] == L::type(v), MHA_ERR_INVALID, "basis type of variable " << v << " does not match the module");
-  // as many elements (wavefronts) per workgroup as the LDS holds beside the tables
-  const size_t per_wave = diag_wave_doubles(vl, geo_size<DIM>(), coupling_size<L, DIM>()) * sizeof(double);
-  const size_t tables = vl.tables_size * sizeof(double);
-  MHA_REQUIRE(tables + per_wave <= kDiagLdsLimit, MHA_ERR_INVALID,
-              "element needs " << tables + per_wave << " B of LDS (limit 160 KB)");
-  const int nw = static_cast<int>(std::min<size_t>(kDiagMaxWaves, (kDiagLdsLimit - tables) / per_wave));
-  const size_t lds = tables + nw * per_wave;
-  const int num_cu = current_device_num_cus();
-  const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(size_t(4), kDiagLdsLimit / lds)));
-  const int grid = std::max(1, std::min((b.e_count + nw - 1) / nw, num_cu * per_cu));
-  if (lds_bytes) *lds_bytes = lds;
-  if (waves) *waves = nw;
-  auto go = [&](auto kern) {
-    require_modest_scratch(kern, "Jacobian diagonal");
-    MHA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(kDiagLdsLimit)));
+  require_layout<PHYS, DIM>(vl);
+  const WaveLaunch g = wave_launch(vl.tables_size * sizeof(double),
+                                   diag_wave_doubles(vl, geo_size<DIM>(), coupling_size<L, DIM>()) * sizeof(double), b.e_count);
+  if (lds_bytes) *lds_bytes = g.lds;
+  if (waves) *waves = g.nw;
+  dispatch_expr<PHYS>(pp, [&](auto expr) {
+    auto kern = jacobian_diagonal_kernel<DIM, PHYS, decltype(expr)::value>;
+    prepare_kernel(kern, "Jacobian diagonal");
     if (overwrite) MHA_HIP(hipMemsetAsync(d, 0, sizeof(double) * b.nrows, stream));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * nw), lds, stream, b, vl, pp, tm, d);
+    hipLaunchKernelGGL(kern, dim3(g.grid), dim3(64 * g.nw), g.lds, stream, b, vl, pp, tm, d);
     MHA_HIP(hipGetLastError());
-  };
-  if (uses_fields(pp)) {
-    // deck strings that read the solution fields: built for the modules whose point function has an EXPR = 2 form
-    if constexpr (PHYS == MHA_PHYSICS_THERMAL || PHYS == MHA_PHYSICS_CDR || PHYS == MHA_PHYSICS_NAVIERSTOKES_CDR) {
-      go(jacobian_diagonal_kernel<DIM, PHYS, 2>);
-    } else {
-      MHA_REQUIRE(false, MHA_ERR_INVALID, "functions of the solution fields are built for the thermal module");
-    }
-  } else if (PHYS == MHA_PHYSICS_POROUS_MIXED && (pp.het.edata || pp.het.kl)) {
-    if constexpr (PHYS == MHA_PHYSICS_POROUS_MIXED) {
-      MHA_REQUIRE(!has_expression(pp), MHA_ERR_INVALID,
-                  "porousMixed: heterogeneous permeability with deck-string functions is not built; give source / mobility as constants or closed forms");
-      go(jacobian_diagonal_kernel<DIM, PHYS, 3>);
-    }
-  } else if (has_expression(pp)) {
-    go(jacobian_diagonal_kernel<DIM, PHYS, 1>);
-  } else {
-    go(jacobian_diagonal_kernel<DIM, PHYS, 0>);
-  }
+  });
 }
 
 }  // namespace
@@ -244,32 +171,9 @@ void launch_jacobian_diagonal(const BlockDev &b, const VarLayoutDev &vl, const P
     if (overwrite) MHA_HIP(hipMemsetAsync(d, 0, sizeof(double) * b.nrows, stream));
     return;
   }
-  static_assert(MHA_PHYSICS_HELMHOLTZ < 100, "the switch key holds two decimal digits of module id");
-#define MHA_DIAG_CASE(D, P) \
-  case D * 100 + P: launch_typed<D, P>(b, vl, pp, tm, d, overwrite, stream, lds_bytes, waves); break;
-  switch (b.dim * 100 + pp.physics) {
-    MHA_DIAG_CASE(2, MHA_PHYSICS_THERMAL)
-    MHA_DIAG_CASE(3, MHA_PHYSICS_THERMAL)
-    MHA_DIAG_CASE(2, MHA_PHYSICS_POROUS_MIXED)
-    MHA_DIAG_CASE(3, MHA_PHYSICS_POROUS_MIXED)
-    MHA_DIAG_CASE(2, MHA_PHYSICS_NAVIERSTOKES)
-    MHA_DIAG_CASE(3, MHA_PHYSICS_NAVIERSTOKES)
-    MHA_DIAG_CASE(2, MHA_PHYSICS_NAVIERSTOKES_THERMAL)
-    MHA_DIAG_CASE(3, MHA_PHYSICS_NAVIERSTOKES_THERMAL)
-    MHA_DIAG_CASE(2, MHA_PHYSICS_LINEARELASTICITY)
-    MHA_DIAG_CASE(3, MHA_PHYSICS_LINEARELASTICITY)
-    MHA_DIAG_CASE(2, MHA_PHYSICS_LINEARELASTICITY_THERMAL)
-    MHA_DIAG_CASE(3, MHA_PHYSICS_LINEARELASTICITY_THERMAL)
-    MHA_DIAG_CASE(2, MHA_PHYSICS_CDR)
-    MHA_DIAG_CASE(3, MHA_PHYSICS_CDR)
-    MHA_DIAG_CASE(2, MHA_PHYSICS_NAVIERSTOKES_CDR)
-    MHA_DIAG_CASE(3, MHA_PHYSICS_NAVIERSTOKES_CDR)
-    MHA_DIAG_CASE(2, MHA_PHYSICS_HELMHOLTZ)
-    MHA_DIAG_CASE(3, MHA_PHYSICS_HELMHOLTZ)
-    MHA_DIAG_CASE(2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED)
-    default: MHA_REQUIRE(false, MHA_ERR_INVALID, "no Jacobian-diagonal kernel for physics " << pp.physics << " in " << b.dim << "-D");
-  }
-#undef MHA_DIAG_CASE
+  dispatch_module(b.dim, pp.physics, "Jacobian-diagonal", [&](auto dim, auto phys) {
+    launch_typed<decltype(dim)::value, decltype(phys)::value>(b, vl, pp, tm, d, overwrite, stream, lds_bytes, waves);
+  });
 }
 
 }  // namespace mha

@@ -24,6 +24,8 @@
 //     with the accumulators of a column tile for all row panels, P blocks two points ahead, one barrier per point.
 // Output: dense local_J / local_res (updateJac / updateRes convention; the row-gather kernel turns them into CRS rows
 // without global atomics) or atomics into res / CRS through the element-major slot map.
+// Phases 1-3 state what they have in common with the matrix-free kernels through engine_points.hpp's macros; the module
+// list, the layout check and the choice of EXPR are engine_dispatch.hpp's, the choice of TPE is dispatch_tpe below.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +33,7 @@
 #include <type_traits>
 
 #include "device_math.hpp"
+#include "engine_dispatch.hpp"
 #include "engine_points.hpp"
 #include "launch.hpp"
 
@@ -113,18 +116,7 @@ __global__ __launch_bounds__(kEngineThreads) void point_engine_kernel(BlockDev b
                3 * ntile * 256 <= NQ * NS * kPanelRows && out_all.compute_jacobian && out_all.local_J &&
                out_all.local_store && !out_all.crs_vals && !mass_mode && !(dbg_stop & (8 | 32));
   }
-  // layout of the variable that holds slot m / dof f.  The loops run over the module's compile-time variable count, so
-  // the layout arrays are indexed statically (kernel arguments in scalar registers); indexed by a run-time variable
-  // number they are memory loads, one dependent on the other, in every phase of every element
-  struct VarAt { int sp, nsl, card, cp, vp, to; };
-  auto var_at = [&](int key, bool by_slot) {
-    VarAt r = {vl.slotptr[0], vl.nslot[0], vl.card[0], vl.cardpad[0], vl.varptr[0], vl.table_off[0]};
-#pragma unroll
-    for (int k = 1; k < L::nvars; ++k)
-      if (key >= (by_slot ? vl.slotptr[k] : vl.varptr[k]))
-        r = {vl.slotptr[k], vl.nslot[k], vl.card[k], vl.cardpad[k], vl.varptr[k], vl.table_off[k]};
-    return r;
-  };
+  MHA_VAR_AT();
   const int iters = (TPE == 64) ? max(el_end - el_begin, 0) : (((int)blockIdx.x * NG * chunk < b.e_count) ? chunk : 0);
   // q-streamed form: the thread's dof position is the same in every element, and the next element's row id and solution
   // value are requested while this element's products run (three dependent global loads open every element otherwise)
@@ -163,59 +155,19 @@ __global__ __launch_bounds__(kEngineThreads) void point_engine_kernel(BlockDev b
     if (dbg_stop == 1) continue;
     // ---- 2. reference-slot fields: U^(q,m) = sum_dof u_dof T^[q][slot][dof] ----
     for (int idx = gt; idx < NQ * NS; idx += TPE) {
-      const int q = idx / NS, m = idx - q * NS;
-      const VarAt va = var_at(m, true);
-      const int sl = m - va.sp, card = va.card;
-      const double *T = tab + va.to + (q * va.nsl + sl) * va.cp;
-      const double *uu = s_u + va.vp, *ud = s_ud + va.vp;
-      double a = 0.0, ad = 0.0;
-      if (tm.transient) {
-#pragma unroll 4
-        for (int dof = 0; dof < card; ++dof) {
-          a += uu[dof] * T[dof];
-          ad += ud[dof] * T[dof];
-        }
-      } else {  // steady: the time-derivative coefficients are zero
-#pragma unroll 4
-        for (int dof = 0; dof < card; ++dof) a += uu[dof] * T[dof];
-      }
-      s_Uh[idx] = a;
-      s_Udh[idx] = ad;
+      MHA_REF_SLOT(idx);
+      MHA_REF_FIELDS(idx);
     }
     sync();
     if (dbg_stop == 2) continue;
     // ---- 3. point function, one (point, direction) per thread ----
-    double vol = 0.0;
-    for (int q = 0; q < NQ; ++q) vol += s_geo[q * GEO + 2 * DIM * DIM + 1];
-    const double h = (DIM == 2) ? sqrt(vol) : cbrt(vol);  // Workset::getElementSize (workset.cpp:2666-2679)
+    MHA_ELEMENT_SIZE();
     for (int idx = gt; idx < NQ * (NS + 1); idx += TPE) {
       const int q = idx / (NS + 1), m = idx - q * (NS + 1);
-      const double *g = s_geo + q * GEO;
-      const double *J = g, *Ji = g + DIM * DIM;
-      const double det = g[2 * DIM * DIM], w = g[2 * DIM * DIM + 1];
+      MHA_POINT_GEO();
       Dual U[NS], Ud[NS], F[NS];
-#pragma unroll
-      for (int v = 0; v < L::nvars; ++v) {
-        const int type = L::type(v), sp = slotptr_of<L, DIM>(v), ns = slots_of(type, DIM);
-        double ref[1 + DIM], phys[1 + DIM], refd[1 + DIM], physd[1 + DIM], dir[1 + DIM], pdir[1 + DIM];
-#pragma unroll
-        for (int sl = 0; sl < ns; ++sl) {
-          ref[sl] = s_Uh[q * NS + sp + sl];
-          refd[sl] = s_Udh[q * NS + sp + sl];
-          dir[sl] = (m == sp + sl) ? 1.0 : 0.0;
-        }
-        to_phys<DIM>(type, ref, J, Ji, det, phys);
-        to_phys<DIM>(type, refd, J, Ji, det, physd);
-        to_phys<DIM>(type, dir, J, Ji, det, pdir);
-#pragma unroll
-        for (int sl = 0; sl < ns; ++sl) {
-          U[sp + sl] = mk(phys[sl], tm.alpha_u * pdir[sl]);
-          Ud[sp + sl] = value_like(type, sl, DIM) ? mk(physd[sl], tm.alpha_t * pdir[sl]) : mk(0.0);
-        }
-      }
-      PointArgs<DIM> pa;
-      pa.U = U; pa.Ud = Ud; pa.x = g + 2 * DIM * DIM + 2; pa.h = h; pa.dt = tm.dt;
-      pa.transient = tm.transient; pa.e = e; pa.q = q; pa.nq = NQ; pa.pp = &pp;
+      MHA_SEED_POINT((m == sp + sl) ? 1.0 : 0.0);
+      MHA_POINT_ARGS(pa);
       if (mass_mode) {
         // getWeightedMass: F = masswts[var] * value on the value-like slots, nothing on gradients / divergence
 #pragma unroll
@@ -613,77 +565,54 @@ __global__ __launch_bounds__(kEngineThreads) void point_engine_kernel(BlockDev b
   }
 }
 
+// as many elements per workgroup as the LDS holds (8, 4, 2 or 1): TPE = 64, 128, 256 or 512 threads per element
+template <class F>
+void dispatch_tpe(int groups, F &&f) {
+  if (groups == 8) f(std::integral_constant<int, 64>{});
+  else if (groups == 4) f(std::integral_constant<int, 128>{});
+  else if (groups == 2) f(std::integral_constant<int, 256>{});
+  else f(std::integral_constant<int, 512>{});
+}
+
 template <int DIM, int PHYS>
 void launch_typed(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp, const TimeDev &tm,
                   const ElemOut &out, const void *slot, int slot_bytes, hipStream_t stream) {
-  using L = Layout<PHYS, DIM>;
-  MHA_REQUIRE(vl.nvars == L::nvars && vl.ns_tot == L::NS, MHA_ERR_INVALID,
-              "variable layout does not match the physics module (" << vl.nvars << " variables, " << vl.ns_tot
-                                                                    << " slots)");
-  for (int v = 0; v < L::nvars; ++v)
-    MHA_REQUIRE(vl.type[v] == L::type(v), MHA_ERR_INVALID, "basis type of variable " << v << " does not match the module");
+  require_layout<PHYS, DIM>(vl);
   const size_t per_group = engine_group_doubles(vl, geo_size<DIM>()) * sizeof(double);
   const size_t tables = vl.tables_size * sizeof(double);
   // small elements: one wave per element, four elements per workgroup; large ones: the whole workgroup per element
   // as many elements per workgroup as the LDS holds (8, 4, 2 or 1): TPE = 64, 128, 256 or 512 threads per element
   int groups = 1;
   for (int g = kEngineThreads / 64; g >= 1; g >>= 1)
-    if (tables + g * per_group <= 160 * 1024 && (g == 1 || vl.n_tot <= 64)) { groups = g; break; }
+    if (tables + g * per_group <= kPointLdsLimit && (g == 1 || vl.n_tot <= 64)) { groups = g; break; }
   const size_t lds = tables + groups * per_group;
-  MHA_REQUIRE(lds <= 160 * 1024, MHA_ERR_INVALID, "element needs " << lds << " B of LDS (limit 160 KB)");
+  MHA_REQUIRE(lds <= kPointLdsLimit, MHA_ERR_INVALID, "element needs " << lds << " B of LDS (limit 160 KB)");
   const int num_cu = current_device_num_cus();
-  const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(size_t(2), (160 * 1024) / lds)));
+  const int per_cu = static_cast<int>(std::max<size_t>(1, std::min<size_t>(size_t(2), kPointLdsLimit / lds)));
   PhysParamsDev ppd = pp;
   if (const char *st = std::getenv("MHA_ENGINE_STOP")) { if (pp.physics > 0) ppd.p[7] = std::atof(st); }
   const int grid = std::max(1, std::min((b.e_count + groups - 1) / groups, num_cu * per_cu));
   const uint8_t *s8 = (slot && slot_bytes == 1) ? static_cast<const uint8_t *>(slot) : nullptr;
   const uint16_t *s16 = (slot && slot_bytes == 2) ? static_cast<const uint16_t *>(slot) : nullptr;
   auto go = [&](auto kern) {
-    require_modest_scratch(kern, "point engine");
-    MHA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024));
+    prepare_kernel(kern, "point engine");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kEngineThreads), lds, stream, b, vl, ppd, tm, out, s8, s16);
     MHA_HIP(hipGetLastError());
   };
   // compile-time point counts pay for small elements; for large ones the extra unrolling spills (measured: navierstokes
-  // 32^3 9.1 ms with, 7.2 ms without)
+  // 32^3 9.1 ms with, 7.2 ms without); the deck-string and heterogeneous variants take their point count at run time
   const int nq1 = groups < 4 ? 0 : (vl.nq == (DIM == 2 ? 4 : 8)) ? 2 : (vl.nq == (DIM == 2 ? 9 : 27)) ? 3 : 0;
-  auto pick = [&](auto tpe) {
-    constexpr int T = decltype(tpe)::value;
-    if (nq1 == 2) go(point_engine_kernel<DIM, PHYS, T, 2, 0>);
-    else if (nq1 == 3) go(point_engine_kernel<DIM, PHYS, T, 3, 0>);
-    else go(point_engine_kernel<DIM, PHYS, T, 0, 0>);
-  };
-  if (pp.physics > 0 && uses_fields(pp)) {
-    // deck strings that read the solution fields: the Dual interpreter; built for the modules whose point function
-    // has an EXPR = 2 form
-    if constexpr (PHYS == MHA_PHYSICS_THERMAL || PHYS == MHA_PHYSICS_CDR || PHYS == MHA_PHYSICS_NAVIERSTOKES_CDR) {
-      if (groups == 8) go(point_engine_kernel<DIM, PHYS, 64, 0, 2>);
-      else if (groups == 4) go(point_engine_kernel<DIM, PHYS, 128, 0, 2>);
-      else if (groups == 2) go(point_engine_kernel<DIM, PHYS, 256, 0, 2>);
-      else go(point_engine_kernel<DIM, PHYS, 512, 0, 2>);
-    } else {
-      MHA_REQUIRE(false, MHA_ERR_INVALID, "functions of the solution fields are built for the thermal module");
-    }
-  } else if (PHYS == MHA_PHYSICS_POROUS_MIXED && (pp.het.edata || pp.het.kl)) {
-    if constexpr (PHYS == MHA_PHYSICS_POROUS_MIXED) {
-      MHA_REQUIRE(!has_expression(pp), MHA_ERR_INVALID,
-                  "porousMixed: heterogeneous permeability with deck-string functions is not built; give source / mobility as constants or closed forms");
-      if (groups == 8) go(point_engine_kernel<DIM, PHYS, 64, 0, 3>);
-      else if (groups == 4) go(point_engine_kernel<DIM, PHYS, 128, 0, 3>);
-      else if (groups == 2) go(point_engine_kernel<DIM, PHYS, 256, 0, 3>);
-      else go(point_engine_kernel<DIM, PHYS, 512, 0, 3>);
-    }
-  } else if (pp.physics > 0 && has_expression(pp)) {
-    // deck-string functions: the interpreter call costs registers and scratch, so only these instantiations carry it
-    if (groups == 8) go(point_engine_kernel<DIM, PHYS, 64, 0, 1>);
-    else if (groups == 4) go(point_engine_kernel<DIM, PHYS, 128, 0, 1>);
-    else if (groups == 2) go(point_engine_kernel<DIM, PHYS, 256, 0, 1>);
-    else go(point_engine_kernel<DIM, PHYS, 512, 0, 1>);
-  } else if (groups == 8) pick(std::integral_constant<int, 64>());
-  else if (groups == 4) pick(std::integral_constant<int, 128>());
-  else if (groups == 2) go(point_engine_kernel<DIM, PHYS, 256, 0, 0>);
-  else go(point_engine_kernel<DIM, PHYS, 512, 0, 0>);
+  dispatch_expr<PHYS>(pp, [&](auto expr) {
+    constexpr int E = decltype(expr)::value;
+    dispatch_tpe(groups, [&](auto tpe) {
+      constexpr int T = decltype(tpe)::value;
+      if constexpr (E == 0 && T <= 128) {
+        if (nq1 == 2) return go(point_engine_kernel<DIM, PHYS, T, 2, 0>);
+        if (nq1 == 3) return go(point_engine_kernel<DIM, PHYS, T, 3, 0>);
+      }
+      go(point_engine_kernel<DIM, PHYS, T, 0, E>);
+    });
+  });
 }
 
 }  // namespace
@@ -691,30 +620,9 @@ void launch_typed(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev
 void launch_point_engine(const BlockDev &b, const VarLayoutDev &vl, const PhysParamsDev &pp, const TimeDev &tm,
                          const ElemOut &out, const void *slot, int slot_bytes, hipStream_t stream) {
   if (b.e_count <= 0) return;
-  static_assert(MHA_PHYSICS_HELMHOLTZ < 100, "the switch key holds two decimal digits of module id");
-  const int key = b.dim * 100 + (pp.physics < 0 ? -pp.physics : pp.physics);
-  switch (key) {
-    case 200 + MHA_PHYSICS_THERMAL: launch_typed<2, MHA_PHYSICS_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 300 + MHA_PHYSICS_THERMAL: launch_typed<3, MHA_PHYSICS_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 200 + MHA_PHYSICS_POROUS_MIXED: launch_typed<2, MHA_PHYSICS_POROUS_MIXED>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 300 + MHA_PHYSICS_POROUS_MIXED: launch_typed<3, MHA_PHYSICS_POROUS_MIXED>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 200 + MHA_PHYSICS_NAVIERSTOKES: launch_typed<2, MHA_PHYSICS_NAVIERSTOKES>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 300 + MHA_PHYSICS_NAVIERSTOKES: launch_typed<3, MHA_PHYSICS_NAVIERSTOKES>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 200 + MHA_PHYSICS_NAVIERSTOKES_THERMAL: launch_typed<2, MHA_PHYSICS_NAVIERSTOKES_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 300 + MHA_PHYSICS_NAVIERSTOKES_THERMAL: launch_typed<3, MHA_PHYSICS_NAVIERSTOKES_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 200 + MHA_PHYSICS_LINEARELASTICITY: launch_typed<2, MHA_PHYSICS_LINEARELASTICITY>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 300 + MHA_PHYSICS_LINEARELASTICITY: launch_typed<3, MHA_PHYSICS_LINEARELASTICITY>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 200 + MHA_PHYSICS_LINEARELASTICITY_THERMAL: launch_typed<2, MHA_PHYSICS_LINEARELASTICITY_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 300 + MHA_PHYSICS_LINEARELASTICITY_THERMAL: launch_typed<3, MHA_PHYSICS_LINEARELASTICITY_THERMAL>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 200 + MHA_PHYSICS_CDR: launch_typed<2, MHA_PHYSICS_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 300 + MHA_PHYSICS_CDR: launch_typed<3, MHA_PHYSICS_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 200 + MHA_PHYSICS_NAVIERSTOKES_CDR: launch_typed<2, MHA_PHYSICS_NAVIERSTOKES_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 300 + MHA_PHYSICS_NAVIERSTOKES_CDR: launch_typed<3, MHA_PHYSICS_NAVIERSTOKES_CDR>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 200 + MHA_PHYSICS_HELMHOLTZ: launch_typed<2, MHA_PHYSICS_HELMHOLTZ>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 300 + MHA_PHYSICS_HELMHOLTZ: launch_typed<3, MHA_PHYSICS_HELMHOLTZ>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    case 200 + MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED: launch_typed<2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED>(b, vl, pp, tm, out, slot, slot_bytes, stream); break;
-    default: MHA_REQUIRE(false, MHA_ERR_INVALID, "no point-engine kernel for physics " << pp.physics << " in " << b.dim << "-D");
-  }
+  dispatch_module(b.dim, pp.physics, "point-engine", [&](auto dim, auto phys) {
+    launch_typed<decltype(dim)::value, decltype(phys)::value>(b, vl, pp, tm, out, slot, slot_bytes, stream);
+  });
 }
 
 }  // namespace mha

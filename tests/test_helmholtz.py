@@ -124,12 +124,17 @@ def test_physics_id_agrees_with_the_header_and_the_keys_hold_two_digits():
     assert len(set(ids.values())) == len(ids)
     for k, v in mrhyde_amd.api.PHYSICS_IDS.items():
         assert ids[k] == v
-    # the four launchers key on dim * 100 + id
+    # the four launchers' one switch (engine_dispatch.hpp) keys on dim * 100 + id and lists the module in 2-D and 3-D
     kdir = os.path.join(ROOT, "mrhyde_amd", "csrc", "kernels")
+    txt = open(os.path.join(kdir, "engine_dispatch.hpp")).read()
+    assert "static_assert(MHA_PHYSICS_HELMHOLTZ < 100" in txt and "dim * 100 +" in txt and "dim * 10 +" not in txt
+    assert "case D * 100 + P:" in txt and "X(2, MHA_PHYSICS_HELMHOLTZ)" in txt and "X(3, MHA_PHYSICS_HELMHOLTZ)" in txt
+    assert txt.count("MHA_PHYSICS_HELMHOLTZ") >= 3
+    # ... and each of them goes through it, with no key of its own
     for name in ("point_engine.hip", "jacobian_apply.hip", "jacobian_apply_multi.hip", "jacobian_diagonal.hip"):
         txt = open(os.path.join(kdir, name)).read()
-        assert "static_assert(MHA_PHYSICS_HELMHOLTZ < 100" in txt and "dim * 100 +" in txt and "dim * 10 +" not in txt, name
-        assert txt.count("MHA_PHYSICS_HELMHOLTZ") >= 3, name
+        assert '#include "engine_dispatch.hpp"' in txt and "dispatch_module(b.dim, pp.physics, " in txt, name
+        assert "switch (" not in txt and "* 100 +" not in txt and "* 10 +" not in txt, name
 
 
 def test_select_without_a_context_is_refused():
