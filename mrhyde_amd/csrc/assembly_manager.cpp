@@ -8,7 +8,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "linearelasticity.hpp"
 #include "porous_data.hpp"
 #include "porous_plan.hpp"
 #include "row_owner_plan.hpp"
@@ -343,68 +342,10 @@ void AssemblyManager::setGraph(const int32_t *rowptr, const int32_t *colind) {
 }
 
 void AssemblyManager::selectPhysics(int physics_id) {
-  // the module's myvars / mybasistypes must be what the block was created with (physicsInterface.cpp:537-610)
-  auto expect = [&](std::initializer_list<int> types) {
-    bool ok = types.size() == vars_.size();
-    size_t k = 0;
-    for (int t : types) { if (ok && vars_[k].type != t) ok = false; ++k; }
-    return ok;
-  };
-  if (physics_id == MHA_PHYSICS_THERMAL)
-    MHA_REQUIRE(expect({MHA_BASIS_HGRAD}), MHA_ERR_INVALID, "thermal needs one HGRAD variable (e)");
-  else if (physics_id == MHA_PHYSICS_POROUS_MIXED)
-    MHA_REQUIRE(expect({MHA_BASIS_HVOL, MHA_BASIS_HDIV}), MHA_ERR_INVALID,
-                "porousMixed needs the variables p (HVOL) and u (HDIV), in that order");
-  else if (physics_id == MHA_PHYSICS_NAVIERSTOKES)
-    MHA_REQUIRE(dim_ == 2 ? expect({MHA_BASIS_HGRAD, MHA_BASIS_HGRAD, MHA_BASIS_HGRAD})
-                          : expect({MHA_BASIS_HGRAD, MHA_BASIS_HGRAD, MHA_BASIS_HGRAD, MHA_BASIS_HGRAD}),
-                MHA_ERR_INVALID, "navierstokes needs the HGRAD variables ux, pr, uy[, uz], in that order");
-  else if (physics_id == MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED)
-    MHA_REQUIRE(dim_ == 2 && expect({MHA_BASIS_HGRAD, MHA_BASIS_HGRAD, MHA_BASIS_HGRAD}), MHA_ERR_INVALID,
-                "shallowwaterHybridized needs the HGRAD variables H, Hux, Huy in 2-D");
-  else if (physics_id == MHA_PHYSICS_NAVIERSTOKES_THERMAL) {
-    bool ok = static_cast<int>(vars_.size()) == dim_ + 2;
-    for (const auto &vi : vars_) ok = ok && vi.type == MHA_BASIS_HGRAD;
-    MHA_REQUIRE(ok, MHA_ERR_INVALID,
-                "navierstokes+thermal needs the " << dim_ + 2 << " HGRAD variables ux, pr, uy" << (dim_ == 3 ? ", uz" : "")
-                                                   << ", e, in that order");
-  }
-  else if (physics_id == MHA_PHYSICS_LINEARELASTICITY) {
-    bool ok = static_cast<int>(vars_.size()) == dim_;
-    for (const auto &vi : vars_) ok = ok && vi.type == MHA_BASIS_HGRAD;
-    MHA_REQUIRE(ok, MHA_ERR_INVALID,
-                "linearelasticity needs the " << dim_ << " HGRAD variables dx, dy" << (dim_ == 3 ? ", dz" : "")
-                                              << ", in that order (the thermoelastic term of an 'e' variable on the block "
-                                                 "is the module linearelasticity+thermal, MHA_PHYSICS_LINEARELASTICITY_THERMAL)");
-  }
-  else if (physics_id == MHA_PHYSICS_LINEARELASTICITY_THERMAL) {
-    bool ok = static_cast<int>(vars_.size()) == dim_ + 1 && (dim_ == 2 || dim_ == 3);
-    for (const auto &vi : vars_) ok = ok && vi.type == MHA_BASIS_HGRAD;
-    MHA_REQUIRE(ok, MHA_ERR_INVALID,
-                "linearelasticity+thermal needs the " << dim_ + 1 << " HGRAD variables dx, dy" << (dim_ == 3 ? ", dz" : "")
-                                                       << ", e, in that order");
-    for (int d = 1; d < dim_; ++d)
-      MHA_REQUIRE(vars_[d].order == vars_[0].order, MHA_ERR_INVALID,
-                  "linearelasticity+thermal needs the same order on every displacement component (e may have its own)");
-  }
-  else if (physics_id == MHA_PHYSICS_CDR)
-    MHA_REQUIRE(expect({MHA_BASIS_HGRAD}) && (dim_ == 2 || dim_ == 3), MHA_ERR_INVALID,
-                "cdr needs one HGRAD variable (c) in 2-D or 3-D");
-  else if (physics_id == MHA_PHYSICS_NAVIERSTOKES_CDR) {
-    bool ok = static_cast<int>(vars_.size()) == dim_ + 2 && (dim_ == 2 || dim_ == 3);
-    for (const auto &vi : vars_) ok = ok && vi.type == MHA_BASIS_HGRAD;
-    MHA_REQUIRE(ok, MHA_ERR_INVALID,
-                "navierstokes+cdr needs the " << dim_ + 2 << " HGRAD variables ux, pr, uy" << (dim_ == 3 ? ", uz" : "")
-                                               << ", c, in that order");
-  }
-  else if (physics_id == MHA_PHYSICS_HELMHOLTZ) {
-    MHA_REQUIRE(expect({MHA_BASIS_HGRAD, MHA_BASIS_HGRAD}) && (dim_ == 2 || dim_ == 3), MHA_ERR_INVALID,
-                "helmholtz needs the two HGRAD variables ureal, uimag in 2-D or 3-D");
-    // the reference indexes uimag's basis with ureal's loop index (helmholtz.cpp:155-159)
-    MHA_REQUIRE(vars_[0].order == vars_[1].order, MHA_ERR_INVALID, "helmholtz needs the same order on ureal and uimag");
-  }
-  physics_id_ = physics_id;
-  physics_ = import_physics(physics_id, dim_);
+  // a refused select (unknown id, a variable list the module does not take) leaves module and function table as they were
+  std::unique_ptr<PhysicsBase> module = import_physics(physics_id, dim_);
+  module->checkVariables(dim_, vars_);
+  physics_ = std::move(module);
   physics_->defineFunctions(functions_);
   physics_->setWorkset(&wkset_);
   // names of the solution fields a deck string may read (Workset::getSolutionField, workset.cpp:314-379) -> slots of
@@ -1014,7 +955,7 @@ void AssemblyManager::getMass(const double *masswts, double *local_mass) {
   VarLayoutDev vl = layout_;
   vl.orient = has_orient_ ? d_orient_.data() : nullptr;
   PhysParamsDev pp;
-  pp.physics = -physics_id_;  // negative id = mass mode on the module's variable layout
+  pp.physics = -physics_->id;  // negative id = mass mode on the module's variable layout
   for (size_t v = 0; v < vars_.size(); ++v) pp.p[v] = masswts ? masswts[v] : 1.0;
   ElemOut o;
   o.compute_jacobian = 1;
@@ -1497,6 +1438,12 @@ BoundaryDev AssemblyManager::boundaryDev(const BoundaryGroupData &g) const {
   return b;
 }
 
+void AssemblyManager::checkModuleGroup(int bc_type, const std::string &sidename) const {
+  const GroupQuery g{bc_type, sidename, dim_, n_, order_, side_ref_.nqs, vars_, functions_};
+  if (physics_) physics_->checkBoundaryGroup(g);
+  else PhysicsBase::defaultBoundaryGroupRule(g);
+}
+
 // reference: the BoundaryGroup constructor keeps (localElemID, localSideID, sidename) of one side set
 // (src/tools/boundaryGroup.cpp:25-108); the BC type is what bcs(var, side) holds for it.
 int AssemblyManager::addBoundaryGroup(const std::string &sidename, int bc_type, int num, const int32_t *elem_ids,
@@ -1505,59 +1452,7 @@ int AssemblyManager::addBoundaryGroup(const std::string &sidename, int bc_type, 
   MHA_REQUIRE(bc_type == MHA_BC_NEUMANN || bc_type == MHA_BC_WEAK_DIRICHLET || bc_type == MHA_BC_INTERFACE ||
                   (bc_type >= MHA_BC_SWH_INTERFACE && bc_type <= MHA_BC_SWH_SLIP),
               MHA_ERR_INVALID, "boundary-condition type must be one of MHA_BC_*");
-  MHA_REQUIRE(num >= 0 && (num == 0 || (elem_ids && side_ids)), MHA_ERR_INVALID, "bad boundary entry arrays");
-  MHA_REQUIRE(!sidename.empty(), MHA_ERR_INVALID, "side name is empty");
-  // the thermal boundary kernels are written for a one-variable block: refused, not run against the wrong variable
-  MHA_REQUIRE(physics_id_ != MHA_PHYSICS_NAVIERSTOKES_THERMAL, MHA_ERR_INVALID,
-              "navierstokes+thermal: thermal boundary groups (Neumann, weak Dirichlet, interface on e) are not built for "
-              "the coupled block; strong Dirichlet rows and the generic Flux condition are");
-  MHA_REQUIRE(physics_id_ != MHA_PHYSICS_NAVIERSTOKES_CDR, MHA_ERR_INVALID,
-              "navierstokes+cdr: boundary groups of the modules (Neumann, weak Dirichlet, interface) are not built for the "
-              "coupled block; strong Dirichlet rows and the generic Flux condition are");
-  prepareSideTables();
-  for (int k = 0; k < num; ++k) {
-    MHA_REQUIRE(elem_ids[k] >= 0 && elem_ids[k] < nelem_, MHA_ERR_INVALID,
-                "boundary entry " << k << ": element id " << elem_ids[k] << " out of range");
-    MHA_REQUIRE(side_ids[k] >= 0 && side_ids[k] < side_ref_.nsides, MHA_ERR_INVALID,
-                "boundary entry " << k << ": local side id " << side_ids[k] << " out of range");
-  }
-  if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY_THERMAL) {
-    MHA_REQUIRE(bc_type == MHA_BC_NEUMANN, MHA_ERR_INVALID,
-                "linearelasticity+thermal: boundary groups are MHA_BC_NEUMANN (traction on the displacements); weak-Dirichlet "
-                "and interface groups (MHA_BC_WEAK_DIRICHLET, MHA_BC_INTERFACE: their side stress needs the thermoelastic "
-                "term at the side points) and thermal's groups on e are not built for the coupled block");
-    MHA_REQUIRE(vars_[0].order == order_, MHA_ERR_INVALID,
-                "linearelasticity+thermal: traction groups need the order of e not above the displacements'");
-    MHA_REQUIRE(linearelasticity_boundary_supported(dim_, dim_ * vars_[0].card, side_ref_.nqs), MHA_ERR_INVALID,
-                "linearelasticity boundary terms are not available for " << vars_[0].card << " dofs per component with "
-                                                                         << side_ref_.nqs << " side integration points");
-  } else if (physics_id_ == MHA_PHYSICS_HELMHOLTZ) {
-    MHA_REQUIRE(bc_type == MHA_BC_NEUMANN, MHA_ERR_INVALID,
-                "helmholtz: boundary groups are MHA_BC_NEUMANN (the Robin condition of helmholtz.cpp:320-375); "
-                "weak-Dirichlet and interface groups are not built");
-    MHA_REQUIRE(helmholtz_boundary_supported(dim_, n_, side_ref_.nqs), MHA_ERR_INVALID,
-                "helmholtz boundary terms are not available for " << n_ << " dofs per element with " << side_ref_.nqs
-                                                                  << " side integration points");
-  } else if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY) {
-    MHA_REQUIRE(bc_type == MHA_BC_NEUMANN || bc_type == MHA_BC_WEAK_DIRICHLET, MHA_ERR_INVALID,
-                "linearelasticity: boundary groups are MHA_BC_NEUMANN (traction) or MHA_BC_WEAK_DIRICHLET; the interface "
-                "condition (MHA_BC_INTERFACE) is not built");
-    MHA_REQUIRE(linearelasticity_boundary_supported(dim_, n_, side_ref_.nqs), MHA_ERR_INVALID,
-                "linearelasticity boundary terms are not available for " << n_ << " dofs per element with "
-                                                                         << side_ref_.nqs << " side integration points");
-  } else {
-    MHA_REQUIRE(thermal_boundary_supported(n_, side_ref_.nqs), MHA_ERR_INVALID,
-                "boundary terms are not available for " << n_ << " dofs per element with " << side_ref_.nqs
-                                                        << " side integration points");
-  }
-  std::unique_ptr<BoundaryGroupData> g(new BoundaryGroupData());
-  g->sidename = sidename;
-  g->bc_type = bc_type;
-  g->num = num;
-  g->elem.upload(elem_ids, num);
-  g->side.upload(side_ids, num);
-  boundary_groups_.push_back(std::move(g));
-  return static_cast<int>(boundary_groups_.size()) - 1;
+  return keepGroup(bc_type, sidename, -1, num, elem_ids, side_ids);
 }
 
 // reference: wkset->var_bcs(var, side) == "Flux" / "Dirichlet" for `varname` on this side set (physicsInterface.cpp:1705-1712,
@@ -1567,6 +1462,12 @@ int AssemblyManager::addVarGroup(int bc_type, const std::string &sidename, const
   MHA_REQUIRE(has_mesh_, MHA_ERR_STATE, "no mesh: call mha_set_mesh first");
   const int var = varIndex(varname);
   MHA_REQUIRE(var >= 0, MHA_ERR_INVALID, "the block has no variable named '" << varname << "'");
+  return keepGroup(bc_type, sidename, var, num, elem_ids, side_ids);
+}
+
+// the checks of the entries; a group of the modules (var < 0) is put to the module's rule; then the group is kept
+int AssemblyManager::keepGroup(int bc_type, const std::string &sidename, int var, int num, const int32_t *elem_ids,
+                               const int32_t *side_ids) {
   MHA_REQUIRE(num >= 0 && (num == 0 || (elem_ids && side_ids)), MHA_ERR_INVALID, "bad boundary entry arrays");
   MHA_REQUIRE(!sidename.empty(), MHA_ERR_INVALID, "side name is empty");
   prepareSideTables();
@@ -1576,6 +1477,7 @@ int AssemblyManager::addVarGroup(int bc_type, const std::string &sidename, const
     MHA_REQUIRE(side_ids[k] >= 0 && side_ids[k] < side_ref_.nsides, MHA_ERR_INVALID,
                 "boundary entry " << k << ": local side id " << side_ids[k] << " out of range");
   }
+  if (var < 0) checkModuleGroup(bc_type, sidename);
   std::unique_ptr<BoundaryGroupData> g(new BoundaryGroupData());
   g->sidename = sidename;
   g->bc_type = bc_type;
@@ -1714,33 +1616,15 @@ void AssemblyManager::assembleBoundary(int flags, const double *u, const double 
   MHA_REQUIRE(res != nullptr, MHA_ERR_INVALID, "residual vector is null");
   MHA_REQUIRE(!compute_jacobian || crs_vals, MHA_ERR_INVALID, "compute_jacobian set but crs_vals is null");
   bindState(u, u_prev, u_stage);
-  // (groups added before the coupled module was selected: refused before anything is written)
-  if (physics_id_ == MHA_PHYSICS_NAVIERSTOKES_THERMAL)
-    for (const auto &g : boundary_groups_)
-      MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX, MHA_ERR_INVALID,
-                  "navierstokes+thermal: thermal boundary groups are not built for the coupled block (group '" << g->sidename << "')");
-  if (physics_id_ == MHA_PHYSICS_NAVIERSTOKES_CDR)
-    for (const auto &g : boundary_groups_)
-      MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX, MHA_ERR_INVALID,
-                  "navierstokes+cdr: boundary groups of the modules are not built for the coupled block (group '" << g->sidename << "')");
-  if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY_THERMAL)
-    for (const auto &g : boundary_groups_) {
-      MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX || g->bc_type == MHA_BC_NEUMANN, MHA_ERR_INVALID,
-                  "linearelasticity+thermal: only traction (MHA_BC_NEUMANN) groups are built for the coupled block (group '"
-                      << g->sidename << "')");
-      // a Neumann side with data for e is thermal's own condition (thermal.cpp:188-216): not run, and not passed over
-      MHA_REQUIRE(g->bc_type != MHA_BC_NEUMANN || !functions_.has("Neumann e " + g->sidename), MHA_ERR_INVALID,
-                  "linearelasticity+thermal: thermal's boundary groups on e are not built for the coupled block ('Neumann e "
-                      << g->sidename << "' is set); a Neumann group is traction on the displacements");
+  // a group added before the module was selected, or whose side got data since: refused before anything is written
+  for (const auto &g : boundary_groups_) {
+    if (g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX) continue;
+    try {
+      checkModuleGroup(g->bc_type, g->sidename);
+    } catch (const Error &e) {
+      throw Error(e.code, std::string(e.what()) + " (group '" + g->sidename + "')");
     }
-  if (physics_id_ == MHA_PHYSICS_LINEARELASTICITY)
-    for (const auto &g : boundary_groups_)
-      MHA_REQUIRE(g->bc_type != MHA_BC_INTERFACE, MHA_ERR_INVALID,
-                  "linearelasticity: the interface condition (MHA_BC_INTERFACE) is not built (group '" << g->sidename << "')");
-  if (physics_id_ == MHA_PHYSICS_HELMHOLTZ)
-    for (const auto &g : boundary_groups_)
-      MHA_REQUIRE(g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX || g->bc_type == MHA_BC_NEUMANN, MHA_ERR_INVALID,
-                  "helmholtz: only MHA_BC_NEUMANN (Robin) groups are built (group '" << g->sidename << "')");
+  }
   timedBegin();
   for (size_t gi = 0; gi < boundary_groups_.size(); ++gi) {
     const auto &g = boundary_groups_[gi];
@@ -1782,10 +1666,9 @@ const char *AssemblyManager::derivedName(int k) {
 // the integration points, then "VM stress" and "MAG stress".  One launch over all elements; the solution is read as given.
 void AssemblyManager::getDerivedValues(const double *u, double *vm, double *mag, double *stress) {
   requireReady(false);
-  MHA_REQUIRE(!physics_->getDerivedNames().empty(), MHA_ERR_INVALID,
-              "physics module '" << physics_->label << "' has no derived quantities (the stress output is linearelasticity's)");
-  MHA_REQUIRE(u != nullptr, MHA_ERR_INVALID, "solution vector is null");
   LeStressDev a;
+  const bool has_e = physics_->stressSettings(a);  // refuses a module without a stress output
+  MHA_REQUIRE(u != nullptr, MHA_ERR_INVALID, "solution vector is null");
   for (int d = 1; d < dim_; ++d)
     MHA_REQUIRE(vars_[d].card == vars_[0].card, MHA_ERR_INVALID,
                 "the stress output needs the same order on every displacement component");
@@ -1795,18 +1678,12 @@ void AssemblyManager::getDerivedValues(const double *u, double *vm, double *mag,
   a.orient = pu.orient;
   a.lam = functions_.evaluate("lambda");
   a.mu = functions_.evaluate("mu");
-  if (const auto *le = dynamic_cast<const linearelasticity *>(physics_.get())) {
-    a.plane_stress = le->incplanestress && dim_ == 2 ? 1 : 0;
-  } else if (const auto *te = dynamic_cast<const linearelasticityThermal *>(physics_.get())) {
+  a.plane_stress = a.plane_stress && dim_ == 2 ? 1 : 0;
+  if (has_e) {
     const VarPointsDev pe = varPoints(dim_, false);
     a.card_e = pe.card;
     a.off_e = pe.var_off;
     a.val_e = pe.val;
-    a.plane_stress = te->incplanestress && dim_ == 2 ? 1 : 0;
-    a.alpha_T = te->alpha_T;
-    a.T_ambient = te->T_ambient;
-  } else {
-    MHA_REQUIRE(false, MHA_ERR_INVALID, "physics module '" << physics_->label << "' has no stress output");
   }
   a.u = u;
   a.vm = vm;
@@ -1826,8 +1703,7 @@ void AssemblyManager::computeFlux(int group, const double *u, const double *u_pr
   MHA_REQUIRE(group >= 0 && group < numBoundaryGroups(), MHA_ERR_INVALID, "boundary group id out of range");
   MHA_REQUIRE(flux != nullptr, MHA_ERR_INVALID, "flux array is null");
   const auto &g = boundary_groups_[group];
-  bindState(u, u_prev, u_stage);
-  if (physics_id_ != MHA_PHYSICS_NAVIERSTOKES) prepareSideTables();
+  bindState(u, u_prev, u_stage);  // (the side tables were made when the group was added)
   wkset_.sidename = g->sidename;
   wkset_.current_bc = g->bc_type;
   wkset_.bnd = boundaryDev(*g);

@@ -31,7 +31,7 @@ class AssemblyManager {
   // (SolverManager::setDirichlet, solverManager.cpp:1876-1957)
   void dirichletLift(double *u, const double *vals, double scalar);
   // modules whose volume term only exists as a point function (multi-variable blocks; thermal with advection)
-  bool engineOnly() const { return physics_id_ != MHA_PHYSICS_THERMAL || (physics_ && physics_->pointEngineOnly()); }
+  bool engineOnly() const { return physics_->pointEngineOnly(); }
   void setMesh(int nelem, const double *nodes, const int32_t *lids, const int32_t *offsets, int nrows,
                const uint8_t *fixed);
   void setOrientation(const int8_t *signs);
@@ -147,10 +147,8 @@ class AssemblyManager {
 
   int dim_ = 0, order_ = 0, qdeg_ = 0, n_ = 0, nq_ = 0, nnodes_ = 0;  // n_ = dofs per element over all variables
   // variables of the block (GroupMetaData::basis_types / basis orders; wkset->usebasis) and the point engine's tables
-  struct VarInfo { int type, order, card; };
   std::vector<VarInfo> vars_;
   bool single_hgrad_ = true;  // the thermal kernels of thermal_*.hip need one HGRAD variable
-  int physics_id_ = 0;
   std::vector<std::string> derived_names_;  // storage behind derivedName()
   VarLayoutDev layout_;
   DeviceBuffer<double> d_slot_tables_;
@@ -315,6 +313,7 @@ class AssemblyManager {
   VarPointsDev varPoints(int v, bool side);
   int addVarGroup(int bc_type, const std::string &sidename, const std::string &varname, int num, const int32_t *elem_ids,
                   const int32_t *side_ids);
+  int keepGroup(int bc_type, const std::string &sidename, int var, int num, const int32_t *elem_ids, const int32_t *side_ids);
   void initialFunctions(int v, FuncDesc f[3]) const;
   // basis arrays of variable v on the current workset (aliases the single-variable views of the workset)
   void worksetVarArrays(int v, const double **basis, const double **grad, const double **div) const;
@@ -337,6 +336,8 @@ class AssemblyManager {
   void prepareSideTables();
   SideTablesDev sideTablesDev() const;
   BoundaryDev boundaryDev(const BoundaryGroupData &g) const;
+  // the selected module's rule for a group of the modules (PhysicsBase::checkBoundaryGroup), the default one without a module
+  void checkModuleGroup(int bc_type, const std::string &sidename) const;
 
   // scratch of the two-step (updateJac/scatterJac) path, one workset wide
   DeviceBuffer<double> d_local_J_, d_local_res_;

@@ -557,6 +557,24 @@ int mha_test_swhdg_check_subgrids(int m, int num_elems, int num_rows, const doub
   return guarded([&] { mha::check_swhdg_subgrids(m, num_elems, num_rows, nodes, lids, offsets); });
 }
 
+int mha_test_module_rules(int physics_id, int dim, int num_vars, const int32_t *types, const int32_t *orders,
+                          const int32_t *cards, int bc_type, const char *sidename, int n, int block_order, int nqs,
+                          int define_neumann_e) {
+  return guarded([&] {
+    MHA_REQUIRE(num_vars >= 0 && (num_vars == 0 || (types && orders && cards)) && sidename, MHA_ERR_INVALID, "null argument");
+    std::vector<mha::VarInfo> vars;
+    for (int v = 0; v < num_vars; ++v) vars.push_back({types[v], orders[v], cards[v]});
+    mha::FunctionManager fm;
+    if (define_neumann_e) fm.addFunction(std::string("Neumann e ") + sidename, mha::FuncDesc());
+    const std::string side = sidename;
+    const mha::GroupQuery g{bc_type, side, dim, n, block_order, nqs, vars, fm};
+    if (bc_type != 0 && physics_id == 0) return mha::PhysicsBase::defaultBoundaryGroupRule(g);
+    const std::unique_ptr<mha::PhysicsBase> module = mha::import_physics(physics_id, dim);
+    if (bc_type == 0) return module->checkVariables(dim, vars);
+    module->checkBoundaryGroup(g);
+  });
+}
+
 int mha_swhdg_condensed_subgrid(mha_context *ctx, const double *u, const double *u_prev, const double *u_stage,
                                 const double *lambda, const uint8_t *side_types, const double *farfield_host, double *schur,
                                 double *gvec, double *du, int32_t *num_singular) {

@@ -36,6 +36,7 @@ cdr::cdr() {
   label = "cdr";
   myvars = {"c"};            // reference: cdr.cpp:22
   mybasistypes = {"HGRAD"};  // reference: cdr.cpp:23
+  needs = "one HGRAD variable (c) in 2-D or 3-D";
 }
 
 void cdr::defineFunctions(FunctionManager &fm) {
@@ -69,6 +70,7 @@ navierstokesCdr::navierstokesCdr(int dim) {
   if (dim == 2) myvars = {"ux", "pr", "uy", "c"};  // navierstokes.cpp:27-34 followed by cdr.cpp:22
   else myvars = {"ux", "pr", "uy", "uz", "c"};
   mybasistypes.assign(myvars.size(), "HGRAD");
+  needs = dim == 3 ? "the 5 HGRAD variables ux, pr, uy, uz, c, in that order" : "the 4 HGRAD variables ux, pr, uy, c, in that order";
 }
 
 // both modules' defineFunctions (navierstokes.cpp:62-76, cdr.cpp:40-48) on one function manager: "density" is registered
@@ -121,7 +123,7 @@ void navierstokesCdr::volumeResidual() {
 
 // neither module has a boundary term here (navierstokes' are not built, cdr's are empty in the reference): a group of the
 // modules on this block is refused rather than passed over
-void navierstokesCdr::boundaryResidual() {
+void navierstokesCdr::checkBoundaryGroup(const GroupQuery &) const {
   throw Error(MHA_ERR_INVALID,
               "navierstokes+cdr: boundary groups of the modules (Neumann, weak Dirichlet, interface) are not built for the "
               "coupled block; strong Dirichlet rows and the generic Flux condition are");

@@ -28,9 +28,9 @@ class cdr : public PhysicsBase {
 class navierstokesCdr : public PhysicsBase {
  public:
   explicit navierstokesCdr(int dim);
+  void checkBoundaryGroup(const GroupQuery &g) const override;
   void defineFunctions(FunctionManager &fm) override;
   void volumeResidual() override;
-  void boundaryResidual() override;
   void computeFlux() override;
   void setParameter(const std::string &name, double value) override;
   bool useSUPG = false, usePSPG = false;  // navierstokes.cpp:45-46

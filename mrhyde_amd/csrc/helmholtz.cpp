@@ -16,6 +16,25 @@ helmholtz::helmholtz() {
   label = "helmholtz";
   myvars = {"ureal", "uimag"};        // reference: helmholtz.cpp:24-25
   mybasistypes = {"HGRAD", "HGRAD"};  // reference: helmholtz.cpp:26-27
+  needs = "the two HGRAD variables ureal, uimag in 2-D or 3-D";
+}
+
+void helmholtz::checkVariables(int dim, const std::vector<VarInfo> &vars) const {
+  PhysicsBase::checkVariables(dim, vars);
+  // the reference indexes uimag's basis with ureal's loop index (helmholtz.cpp:155-159)
+  MHA_REQUIRE(vars[0].order == vars[1].order, MHA_ERR_INVALID, "helmholtz needs the same order on ureal and uimag");
+}
+
+// reference: helmholtz::boundaryResidual (helmholtz.cpp:254-419): a side whose condition on ureal is "Neumann" gets the
+// Robin terms on both rows (:320); every other type adds nothing there.  Weak-Dirichlet and interface groups, which the
+// reference passes over, are refused rather than silently dropped.
+void helmholtz::checkBoundaryGroup(const GroupQuery &g) const {
+  MHA_REQUIRE(g.bc_type == MHA_BC_NEUMANN, MHA_ERR_INVALID,
+              "helmholtz: boundary groups are MHA_BC_NEUMANN (the Robin condition of helmholtz.cpp:320-375); "
+              "weak-Dirichlet and interface groups are not built");
+  MHA_REQUIRE(helmholtz_boundary_supported(g.dim, g.n, g.nqs), MHA_ERR_INVALID,
+              "helmholtz boundary terms are not available for " << g.n << " dofs per element with " << g.nqs
+                                                                << " side integration points");
 }
 
 // reference: helmholtz::defineFunctions (helmholtz.cpp:41-70): every function defaults to "0.0".  omegar, omegai, the
@@ -59,8 +78,6 @@ void helmholtz::volumeFunctions(PhysParamsDev &pp, int dim) const {
 void helmholtz::volumeResidual() {
   MHA_REQUIRE(wkset != nullptr, MHA_ERR_STATE, "helmholtz::volumeResidual called without a workset");
   Workset &w = *wkset;
-  MHA_REQUIRE(w.layout.nvars == 2 && w.layout.card[0] == w.layout.card[1], MHA_ERR_INVALID,
-              "helmholtz needs the same order on ureal and uimag");
   BlockDev b = w.dev;
   b.e_begin = w.first_elem;
   b.e_count = w.numElem;
@@ -69,17 +86,10 @@ void helmholtz::volumeResidual() {
   launch_volume_points(w, b, pp);
 }
 
-// reference: helmholtz::boundaryResidual (helmholtz.cpp:254-419): a side whose condition on ureal is "Neumann" gets the
-// Robin terms on both rows (:320); every other type adds nothing there.  Weak-Dirichlet and interface groups, which the
-// reference passes over, are refused rather than silently dropped.
+// the Robin terms of a Neumann group (checkBoundaryGroup has refused every other type)
 void helmholtz::boundaryResidual() {
   MHA_REQUIRE(wkset != nullptr, MHA_ERR_STATE, "helmholtz::boundaryResidual called without a workset");
   Workset &w = *wkset;
-  MHA_REQUIRE(w.current_bc == MHA_BC_NEUMANN, MHA_ERR_INVALID,
-              "helmholtz: boundary groups are MHA_BC_NEUMANN (the Robin condition); weak-Dirichlet and interface groups "
-              "are not built");
-  MHA_REQUIRE(w.layout.nvars == 2 && w.layout.card[0] == w.layout.card[1], MHA_ERR_INVALID,
-              "helmholtz needs the same order on ureal and uimag");
   HelmholtzBoundaryDev hb;
   for (int k = 0; k < 10; ++k) {
     if (w.dimension == 2 && (k == 4 || k == 5)) continue;

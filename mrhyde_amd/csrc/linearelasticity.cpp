@@ -2,11 +2,40 @@
 
 namespace mha {
 
+namespace {
+
+// The constructor's options (linearelasticity.cpp:42-58) whose terms are not built, on both elasticity modules: accepted
+// at the value that leaves them off and refused otherwise.  false: `name` is none of them.
+bool unbuilt_option(const std::string &label, const std::string &name, double value) {
+  if (name == "use crystal elasticity")
+    MHA_REQUIRE(value == 0.0, MHA_ERR_INVALID, label << ": 'use crystal elasticity' is not built (CrystalElastic::computeStress)");
+  else if (name == "Biot")
+    MHA_REQUIRE(value == 0.0, MHA_ERR_INVALID, label << ": 'Biot' (the pressure term of a poroelastic block) is not built");
+  else if (name == "use Lame parameters")
+    MHA_REQUIRE(value != 0.0, MHA_ERR_INVALID, label << ": 'use Lame parameters' = 0 is not built; give 'lambda' and 'mu'");
+  else return false;
+  return true;
+}
+
+}  // namespace
+
 linearelasticity::linearelasticity(int dim) {
   label = "linearelasticity";
   if (dim == 2) myvars = {"dx", "dy"};  // reference: linearelasticity.cpp:33-40
   else myvars = {"dx", "dy", "dz"};
   mybasistypes.assign(myvars.size(), "HGRAD");
+  needs = std::string(dim == 2 ? "the 2 HGRAD variables dx, dy" : "the 3 HGRAD variables dx, dy, dz") +
+          ", in that order (the thermoelastic term of an 'e' variable on the block is the module linearelasticity+thermal, "
+          "MHA_PHYSICS_LINEARELASTICITY_THERMAL)";
+}
+
+void linearelasticity::checkBoundaryGroup(const GroupQuery &g) const {
+  MHA_REQUIRE(g.bc_type == MHA_BC_NEUMANN || g.bc_type == MHA_BC_WEAK_DIRICHLET, MHA_ERR_INVALID,
+              "linearelasticity: boundary groups are MHA_BC_NEUMANN (traction) or MHA_BC_WEAK_DIRICHLET; the interface "
+              "condition (MHA_BC_INTERFACE) is not built");
+  MHA_REQUIRE(linearelasticity_boundary_supported(g.dim, g.n, g.nqs), MHA_ERR_INVALID,
+              "linearelasticity boundary terms are not available for " << g.n << " dofs per element with " << g.nqs
+                                                                       << " side integration points");
 }
 
 // reference: linearelasticity::defineFunctions (linearelasticity.cpp:72-76): lambda 1, mu 0.5, sources 0
@@ -19,20 +48,12 @@ void linearelasticity::defineFunctions(FunctionManager &fm) {
     if (!fm.has(k)) fm.addFunction(k, constant(0.0));
 }
 
-// reference: the constructor's settings (linearelasticity.cpp:42-58).  The options whose terms are not built are
-// accepted at the value that leaves them off and refused otherwise.
+// reference: the constructor's settings (linearelasticity.cpp:42-58)
 void linearelasticity::setParameter(const std::string &name, double value) {
   if (name == "incplanestress") incplanestress = value != 0.0;
   else if (name == "form_param") formparam = value;
   else if (name == "penalty") penalty = value;
-  else if (name == "use crystal elasticity")
-    MHA_REQUIRE(value == 0.0, MHA_ERR_INVALID, "linearelasticity: 'use crystal elasticity' is not built (CrystalElastic::computeStress)");
-  else if (name == "Biot")
-    MHA_REQUIRE(value == 0.0, MHA_ERR_INVALID, "linearelasticity: 'Biot' (the pressure term of a poroelastic block) is not built");
-  else if (name == "use Lame parameters")
-    MHA_REQUIRE(value != 0.0, MHA_ERR_INVALID,
-                "linearelasticity: 'use Lame parameters' = 0 is not built; give 'lambda' and 'mu'");
-  else PhysicsBase::setParameter(name, value);
+  else if (!unbuilt_option(label, name, value)) PhysicsBase::setParameter(name, value);
 }
 
 // reference: linearelasticity::volumeResidual (linearelasticity.cpp:92-240) as the point function linearelasticity_point
@@ -55,10 +76,7 @@ void linearelasticity::volumeResidual() {
 void linearelasticity::boundaryResidual() {
   MHA_REQUIRE(wkset != nullptr, MHA_ERR_STATE, "linearelasticity::boundaryResidual called without a workset");
   Workset &w = *wkset;
-  MHA_REQUIRE(w.current_bc != MHA_BC_INTERFACE, MHA_ERR_INVALID,
-              "linearelasticity: the interface condition (MHA_BC_INTERFACE, the multiscale weak Dirichlet) is not built");
-  if (w.current_bc != MHA_BC_NEUMANN && w.current_bc != MHA_BC_WEAK_DIRICHLET) return;
-  const bool weak = w.current_bc == MHA_BC_WEAK_DIRICHLET;
+  const bool weak = w.current_bc == MHA_BC_WEAK_DIRICHLET;  // or MHA_BC_NEUMANN: checkBoundaryGroup has refused the rest
   for (int v = 1; v < w.layout.nvars; ++v)
     MHA_REQUIRE(w.layout.card[v] == w.layout.card[0], MHA_ERR_INVALID,
                 "linearelasticity boundary terms need the same order on every component");
@@ -102,6 +120,32 @@ linearelasticityThermal::linearelasticityThermal(int dim) {
   if (dim == 2) myvars = {"dx", "dy", "e"};  // linearelasticity.cpp:33-40 and thermal.cpp:31
   else myvars = {"dx", "dy", "dz", "e"};
   mybasistypes.assign(myvars.size(), "HGRAD");
+  needs = dim == 2 ? "the 3 HGRAD variables dx, dy, e, in that order" : "the 4 HGRAD variables dx, dy, dz, e, in that order";
+}
+
+void linearelasticityThermal::checkVariables(int dim, const std::vector<VarInfo> &vars) const {
+  PhysicsBase::checkVariables(dim, vars);
+  for (int d = 1; d < dim; ++d)
+    MHA_REQUIRE(vars[d].order == vars[0].order, MHA_ERR_INVALID,
+                "linearelasticity+thermal needs the same order on every displacement component (e may have its own)");
+}
+
+// Traction reads no stress: the plain block's kernel on the displacement rows of the coupled element.  Everything else on
+// a side is refused.
+void linearelasticityThermal::checkBoundaryGroup(const GroupQuery &g) const {
+  MHA_REQUIRE(g.bc_type == MHA_BC_NEUMANN, MHA_ERR_INVALID,
+              "linearelasticity+thermal: boundary groups are MHA_BC_NEUMANN (traction on the displacements); weak-Dirichlet "
+              "and interface groups (MHA_BC_WEAK_DIRICHLET, MHA_BC_INTERFACE: their side stress needs the thermoelastic "
+              "term at the side points) and thermal's groups on e are not built for the coupled block");
+  // a Neumann side with data for e is thermal's own condition (thermal.cpp:188-216): not run, and not passed over
+  MHA_REQUIRE(!g.functions.has("Neumann e " + g.sidename), MHA_ERR_INVALID,
+              "linearelasticity+thermal: thermal's boundary groups on e are not built for the coupled block ('Neumann e "
+                  << g.sidename << "' is set); a Neumann group is traction on the displacements");
+  MHA_REQUIRE(g.vars[0].order == g.order, MHA_ERR_INVALID,
+              "linearelasticity+thermal: traction groups need the order of e not above the displacements'");
+  MHA_REQUIRE(linearelasticity_boundary_supported(g.dim, g.dim * g.vars[0].card, g.nqs), MHA_ERR_INVALID,
+              "linearelasticity boundary terms are not available for " << g.vars[0].card << " dofs per component with "
+                                                                       << g.nqs << " side integration points");
 }
 
 // both modules' defineFunctions (linearelasticity.cpp:72-76, thermal.cpp:52-63) on one function manager
@@ -122,14 +166,7 @@ void linearelasticityThermal::setParameter(const std::string &name, double value
   else if (name == "T_ambient") T_ambient = value;
   else if (name == "alpha_T") alpha_T = value;
   else if (name == "include advection") have_advection = value != 0.0;
-  else if (name == "use crystal elasticity")
-    MHA_REQUIRE(value == 0.0, MHA_ERR_INVALID, "linearelasticity+thermal: 'use crystal elasticity' is not built (CrystalElastic::computeStress)");
-  else if (name == "Biot")
-    MHA_REQUIRE(value == 0.0, MHA_ERR_INVALID, "linearelasticity+thermal: 'Biot' (the pressure term of a poroelastic block) is not built");
-  else if (name == "use Lame parameters")
-    MHA_REQUIRE(value != 0.0, MHA_ERR_INVALID,
-                "linearelasticity+thermal: 'use Lame parameters' = 0 is not built; give 'lambda' and 'mu'");
-  else PhysicsBase::setParameter(name, value);
+  else if (!unbuilt_option(label, name, value)) PhysicsBase::setParameter(name, value);
 }
 
 // linearelasticity::volumeResidual with e_num >= 0 and thermal::volumeResidual as ONE point function
@@ -137,9 +174,6 @@ void linearelasticityThermal::setParameter(const std::string &name, double value
 void linearelasticityThermal::volumeResidual() {
   MHA_REQUIRE(wkset != nullptr, MHA_ERR_STATE, "linearelasticity+thermal::volumeResidual called without a workset");
   Workset &w = *wkset;
-  for (int v = 1; v + 1 < w.layout.nvars; ++v)
-    MHA_REQUIRE(w.layout.card[v] == w.layout.card[0], MHA_ERR_INVALID,
-                "linearelasticity+thermal needs the same order on every displacement component");
   BlockDev b = w.dev;
   b.e_begin = w.first_elem;
   b.e_count = w.numElem;
@@ -156,17 +190,10 @@ void linearelasticityThermal::volumeResidual() {
   launch_volume_points(w, b, pp);
 }
 
-// Traction (linearelasticity.cpp:361-371, 419-429, 482-492, 546-556, 609-619) reads no stress: the plain block's kernel
-// on the displacement rows of the coupled element.  Everything else on a side is refused (AssemblyManager::addBoundaryGroup
-// has refused it already unless the group was added before the module was selected).
+// Traction (linearelasticity.cpp:361-371, 419-429, 482-492, 546-556, 609-619), the one group checkBoundaryGroup takes
 void linearelasticityThermal::boundaryResidual() {
   MHA_REQUIRE(wkset != nullptr, MHA_ERR_STATE, "linearelasticity+thermal::boundaryResidual called without a workset");
   Workset &w = *wkset;
-  MHA_REQUIRE(w.current_bc == MHA_BC_NEUMANN, MHA_ERR_INVALID,
-              "linearelasticity+thermal: boundary groups are MHA_BC_NEUMANN (traction on the displacements); weak-Dirichlet "
-              "and interface groups and thermal's groups on e are not built for the coupled block");
-  MHA_REQUIRE(!functionManager->has("Neumann e " + w.sidename), MHA_ERR_INVALID,
-              "linearelasticity+thermal: thermal's boundary groups on e are not built for the coupled block");
   const int dim = w.dimension;
   LeBoundaryDev le;
   for (int d = 0; d < dim; ++d) {

@@ -14,6 +14,8 @@ namespace mha {
 class linearelasticity : public PhysicsBase {
  public:
   explicit linearelasticity(int dim);
+  void checkBoundaryGroup(const GroupQuery &g) const override;
+  bool stressSettings(LeStressDev &a) const override { a.plane_stress = incplanestress; return false; }
   void defineFunctions(FunctionManager &fm) override;
   void volumeResidual() override;
   void boundaryResidual() override;
@@ -36,6 +38,14 @@ class linearelasticity : public PhysicsBase {
 class linearelasticityThermal : public PhysicsBase {
  public:
   explicit linearelasticityThermal(int dim);
+  void checkVariables(int dim, const std::vector<VarInfo> &vars) const override;
+  void checkBoundaryGroup(const GroupQuery &g) const override;
+  bool stressSettings(LeStressDev &a) const override {
+    a.plane_stress = incplanestress;
+    a.alpha_T = alpha_T;
+    a.T_ambient = T_ambient;
+    return true;
+  }
   void defineFunctions(FunctionManager &fm) override;
   void volumeResidual() override;
   void boundaryResidual() override;

@@ -58,17 +58,38 @@ class FunctionManager {
   double time_ = 0.0;
 };
 
+// one variable of a block: basis type (MHA_BASIS_*), order, dofs per element
+struct VarInfo { int type, order, card; };
+
+// a boundary group of the modules as its rule sees it: type, side, and of the block the dofs per element over all
+// variables, its order, the integration points of one side, the variables and the function table
+struct GroupQuery {
+  int bc_type;
+  const std::string &sidename;
+  int dim, n, order, nqs;
+  const std::vector<VarInfo> &vars;
+  const FunctionManager &functions;
+};
+
 class PhysicsBase {
  public:
   virtual ~PhysicsBase() = default;
+  // the module's mybasistypes must be what the block was created with, in that order (physicsInterface.cpp:537-610):
+  // any other variable list is refused with "<label> needs <needs>"; a module with a rule on the orders adds it
+  virtual void checkVariables(int dim, const std::vector<VarInfo> &vars) const;
+  // refuses a boundary group of the module (every type but MHA_BC_DIRICHLET / MHA_BC_FLUX) that boundaryResidual has no
+  // term for; asked when the group is added and again before an assembly writes anything.  The default -- any valid
+  // type, within the sizes kernels/thermal_boundary.hip is built for -- is also the rule of a block without a module.
+  virtual void checkBoundaryGroup(const GroupQuery &g) const { defaultBoundaryGroupRule(g); }
+  static void defaultBoundaryGroupRule(const GroupQuery &g);
   virtual void defineFunctions(FunctionManager &fm) { functionManager = &fm; }
   virtual void volumeResidual() { notImplemented("volumeResidual"); }
   virtual void boundaryResidual() { notImplemented("boundaryResidual"); }
   virtual void faceResidual() { notImplemented("faceResidual"); }
   virtual void computeFlux() { notImplemented("computeFlux"); }
   virtual void setWorkset(Workset *w) { wkset = w; }
-  // true when the current settings need terms only the point-engine form of the module has
-  virtual bool pointEngineOnly() const { return false; }
+  // the volume term exists as a point function only; thermal has element kernels beside it
+  virtual bool pointEngineOnly() const { return true; }
   // refusals of the module's volume functions that an assembly states before it writes anything
   virtual void checkVolumeFunctions(int /*dim*/) const {}
   // scalar settings a module reads from its parameter list in the reference constructor
@@ -81,13 +102,22 @@ class PhysicsBase {
   }
   // reference: getDerivedNames (physicsBase.hpp); the values are AssemblyManager::getDerivedValues
   virtual std::vector<std::string> getDerivedNames() const { return {}; }
+  // the module's settings of the stress output (plane stress; with an "e" variable after the displacements alpha_T and
+  // T_ambient, and true returned); a module without a stress output refuses
+  virtual bool stressSettings(LeStressDev &a) const {
+    MHA_REQUIRE(!getDerivedNames().empty(), MHA_ERR_INVALID,
+                "physics module '" << label << "' has no derived quantities (the stress output is linearelasticity's)");
+    throw Error(MHA_ERR_INVALID, "physics module '" + label + "' has no stress output");
+  }
   // true when the coefficients differ from element to element in a way the geometry database cannot see
   virtual bool heterogeneous() const { return false; }
 
+  int id = 0;  // MHA_PHYSICS_*, set by import_physics
   std::string label;
   Workset *wkset = nullptr;
   FunctionManager *functionManager = nullptr;
   std::vector<std::string> myvars, mybasistypes;
+  std::string needs;  // the variable list in words
 
  protected:
   // the reference prints a message for un-overridden hooks (physicsBase.cpp); we raise
@@ -150,7 +180,7 @@ class porousMixed : public PhysicsBase {
 // (reference: src/physics/navierstokes.hpp, src/physics/navierstokes.cpp:20-849, 1054-1079); myvars {ux, pr, uy[, uz]}
 class navierstokes : public PhysicsBase {
  public:
-  navierstokes();
+  explicit navierstokes(int dim);
   void defineFunctions(FunctionManager &fm) override;
   void volumeResidual() override;
   void computeFlux() override;
@@ -169,9 +199,9 @@ class navierstokes : public PhysicsBase {
 class navierstokesThermal : public PhysicsBase {
  public:
   explicit navierstokesThermal(int dim);
+  void checkBoundaryGroup(const GroupQuery &g) const override;
   void defineFunctions(FunctionManager &fm) override;
   void volumeResidual() override;
-  void boundaryResidual() override;
   void computeFlux() override;
   void setParameter(const std::string &name, double value) override;
   bool useSUPG = false, usePSPG = false;  // navierstokes.cpp:45-46
@@ -187,6 +217,7 @@ class navierstokesThermal : public PhysicsBase {
 class shallowwaterHybridized : public PhysicsBase {
  public:
   shallowwaterHybridized();
+  void checkVariables(int dim, const std::vector<VarInfo> &vars) const override;
   void defineFunctions(FunctionManager &fm) override;
   void volumeResidual() override;
   void boundaryResidual() override;

@@ -100,6 +100,15 @@ int mha_test_porous_database_plan(int num_rows, int num_elems, int n, int nnodes
                                   const int8_t *orient, const uint8_t *fixed, const uint8_t *slot, uint8_t *jacflag,
                                   int32_t *elist, int32_t *diag, int64_t *runs, int64_t runs_len, int64_t *counts);
 
+/* What a physics module accepts, asked of the module import_physics builds for physics_id (csrc/physics.hpp); no block,
+ * no device.  The block's variables are types / orders / cards [num_vars].  bc_type == 0: the variable rule
+ * (PhysicsBase::checkVariables).  Otherwise the boundary-group rule (checkBoundaryGroup; physics_id == 0: the rule of a
+ * block without a module) for a group of that type on `sidename`, on a block of n dofs per element, order block_order
+ * and nqs points per side; define_neumann_e != 0 puts "Neumann e <sidename>" into the function table the rule sees. */
+int mha_test_module_rules(int physics_id, int dim, int num_vars, const int32_t *types, const int32_t *orders,
+                          const int32_t *cards, int bc_type, const char *sidename, int n, int block_order, int nqs,
+                          int define_neumann_e);
+
 #ifdef __cplusplus
 }
 #endif

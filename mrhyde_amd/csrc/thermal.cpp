@@ -83,10 +83,25 @@ void FunctionManager::compileAll() const {
   dirty_ = false;
 }
 
+void PhysicsBase::defaultBoundaryGroupRule(const GroupQuery &g) {
+  MHA_REQUIRE(thermal_boundary_supported(g.n, g.nqs), MHA_ERR_INVALID,
+              "boundary terms are not available for " << g.n << " dofs per element with " << g.nqs
+                                                      << " side integration points");
+}
+
+void PhysicsBase::checkVariables(int dim, const std::vector<VarInfo> &vars) const {
+  static const char *const basis[3] = {"HGRAD", "HVOL", "HDIV"};  // MHA_BASIS_*
+  bool ok = vars.size() == mybasistypes.size();
+  for (size_t v = 0; ok && v < vars.size(); ++v)
+    ok = vars[v].type >= 0 && vars[v].type < 3 && mybasistypes[v] == basis[vars[v].type];
+  MHA_REQUIRE(ok, MHA_ERR_INVALID, label << " needs " << needs);
+}
+
 thermal::thermal() {
   label = "thermal";
   myvars = {"e"};            // reference: thermal.cpp:31
   mybasistypes = {"HGRAD"};  // reference: thermal.cpp:32
+  needs = "one HGRAD variable (e)";
 }
 
 // Defaults of thermal::defineFunctions (reference: src/physics/thermal.cpp:52-63):
@@ -210,6 +225,7 @@ porousMixed::porousMixed() {
   label = "porousMixed";
   myvars = {"p", "u"};               // reference: porousMixed.cpp:33-43
   mybasistypes = {"HVOL", "HDIV"};
+  needs = "the variables p (HVOL) and u (HDIV), in that order";
 }
 
 // reference: porousMixed::defineFunctions (porousMixed.cpp:134-152): source 0, Kinv_* 1, total_mobility 1
@@ -368,10 +384,12 @@ void porousMixed::boundaryResidual() {
 }
 
 // ---- navierstokes ------------------------------------------------------------------------------------------------
-navierstokes::navierstokes() {
+navierstokes::navierstokes(int dim) {
   label = "navierstokes";
-  myvars = {"ux", "pr", "uy", "uz"};  // reference: navierstokes.cpp:27-34 (uz only in 3-D)
-  mybasistypes = {"HGRAD", "HGRAD", "HGRAD", "HGRAD"};
+  myvars = {"ux", "pr", "uy"};  // reference: navierstokes.cpp:27-34 (uz only in 3-D)
+  if (dim != 2) myvars.push_back("uz");
+  mybasistypes.assign(myvars.size(), "HGRAD");
+  needs = "the HGRAD variables ux, pr, uy[, uz], in that order";
 }
 
 // reference: navierstokes::defineFunctions (navierstokes.cpp:62-76): sources 0, density 1, viscosity 1
@@ -434,6 +452,15 @@ navierstokesThermal::navierstokesThermal(int dim) {
   if (dim == 2) myvars = {"ux", "pr", "uy", "e"};  // navierstokes.cpp:27-34 followed by thermal.cpp:31
   else myvars = {"ux", "pr", "uy", "uz", "e"};
   mybasistypes.assign(myvars.size(), "HGRAD");
+  needs = dim == 3 ? "the 5 HGRAD variables ux, pr, uy, uz, e, in that order" : "the 4 HGRAD variables ux, pr, uy, e, in that order";
+}
+
+// thermal::boundaryResidual acts on "e" through kernels written for a one-variable block: out of scope here, and refused
+// rather than run against the wrong variable
+void navierstokesThermal::checkBoundaryGroup(const GroupQuery &) const {
+  throw Error(MHA_ERR_INVALID,
+              "navierstokes+thermal: thermal boundary groups (Neumann, weak Dirichlet, interface on e) are not built for "
+              "the coupled block; strong Dirichlet rows and the generic Flux condition are");
 }
 
 // both modules' defineFunctions (navierstokes.cpp:62-76, thermal.cpp:52-63) on one function manager: "density" is
@@ -481,14 +508,7 @@ void navierstokesThermal::volumeResidual() {
   launch_volume_points(w, b, pp);
 }
 
-// thermal::boundaryResidual / computeFlux act on "e" through kernels written for a one-variable block: out of scope
-// here, and refused rather than run against the wrong variable
-void navierstokesThermal::boundaryResidual() {
-  throw Error(MHA_ERR_INVALID,
-              "navierstokes+thermal: thermal boundary groups (Neumann, weak Dirichlet, interface on e) are not built for "
-              "the coupled block; strong Dirichlet rows and the generic Flux condition are");
-}
-
+// thermal::computeFlux: as the boundary groups
 void navierstokesThermal::computeFlux() {
   throw Error(MHA_ERR_INVALID, "navierstokes+thermal: computeFlux is not built for the coupled block");
 }
@@ -498,6 +518,12 @@ shallowwaterHybridized::shallowwaterHybridized() {
   label = "shallowwaterHybridized";
   myvars = {"H", "Hux", "Huy"};                // reference: shallowwaterHybridized.cpp:41-46
   mybasistypes = {"HGRAD", "HGRAD", "HGRAD"};
+  needs = "the HGRAD variables H, Hux, Huy in 2-D";
+}
+
+void shallowwaterHybridized::checkVariables(int dim, const std::vector<VarInfo> &vars) const {
+  MHA_REQUIRE(dim == 2, MHA_ERR_INVALID, label << " needs " << needs);
+  PhysicsBase::checkVariables(dim, vars);
 }
 
 // reference: shallowwaterHybridized::defineFunctions (:78-108): sources 0
@@ -552,17 +578,20 @@ void shallowwaterHybridized::boundaryResidual() {
 }
 
 std::unique_ptr<PhysicsBase> import_physics(int physics_id, int dim) {
-  if (physics_id == MHA_PHYSICS_NAVIERSTOKES_THERMAL) return std::unique_ptr<PhysicsBase>(new navierstokesThermal(dim));
-  if (physics_id == MHA_PHYSICS_LINEARELASTICITY) return std::unique_ptr<PhysicsBase>(new linearelasticity(dim));
-  if (physics_id == MHA_PHYSICS_LINEARELASTICITY_THERMAL) return std::unique_ptr<PhysicsBase>(new linearelasticityThermal(dim));
-  if (physics_id == MHA_PHYSICS_HELMHOLTZ) return std::unique_ptr<PhysicsBase>(new helmholtz());
-  if (physics_id == MHA_PHYSICS_CDR) return std::unique_ptr<PhysicsBase>(new cdr());
-  if (physics_id == MHA_PHYSICS_NAVIERSTOKES_CDR) return std::unique_ptr<PhysicsBase>(new navierstokesCdr(dim));
-  if (physics_id == MHA_PHYSICS_THERMAL) return std::unique_ptr<PhysicsBase>(new thermal());
-  if (physics_id == MHA_PHYSICS_POROUS_MIXED) return std::unique_ptr<PhysicsBase>(new porousMixed());
-  if (physics_id == MHA_PHYSICS_NAVIERSTOKES) return std::unique_ptr<PhysicsBase>(new navierstokes());
-  if (physics_id == MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED) return std::unique_ptr<PhysicsBase>(new shallowwaterHybridized());
-  throw Error(MHA_ERR_INVALID, "unknown physics module id " + std::to_string(physics_id));
+  std::unique_ptr<PhysicsBase> p;
+  if (physics_id == MHA_PHYSICS_NAVIERSTOKES_THERMAL) p.reset(new navierstokesThermal(dim));
+  if (physics_id == MHA_PHYSICS_LINEARELASTICITY) p.reset(new linearelasticity(dim));
+  if (physics_id == MHA_PHYSICS_LINEARELASTICITY_THERMAL) p.reset(new linearelasticityThermal(dim));
+  if (physics_id == MHA_PHYSICS_HELMHOLTZ) p.reset(new helmholtz());
+  if (physics_id == MHA_PHYSICS_CDR) p.reset(new cdr());
+  if (physics_id == MHA_PHYSICS_NAVIERSTOKES_CDR) p.reset(new navierstokesCdr(dim));
+  if (physics_id == MHA_PHYSICS_THERMAL) p.reset(new thermal());
+  if (physics_id == MHA_PHYSICS_POROUS_MIXED) p.reset(new porousMixed());
+  if (physics_id == MHA_PHYSICS_NAVIERSTOKES) p.reset(new navierstokes(dim));
+  if (physics_id == MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED) p.reset(new shallowwaterHybridized());
+  MHA_REQUIRE(p != nullptr, MHA_ERR_INVALID, "unknown physics module id " << physics_id);
+  p->id = physics_id;
+  return p;
 }
 
 }  // namespace mha

@@ -273,3 +273,62 @@ def test_thermal_compute_flux_and_interface_branch(oracle, dim, order, qdeg, nce
     blk.assemble_boundary(ud, res, vals)
     torch.cuda.synchronize()
     assert rel_err(vals.cpu().numpy(), vals_ref) < RTOL and rel_err(res.cpu().numpy(), res_ref) < RTOL
+
+
+LATE_MODULE_CASES = [  # module, variables of the 2-D block, type of the group added before it, text of the refusal
+    ("navierstokes+thermal", 4, "BC_NEUMANN", "not built for the coupled block"),
+    ("navierstokes+cdr", 4, "BC_NEUMANN", "not built for the coupled block"),
+    ("linearelasticity+thermal", 3, "BC_WEAK_DIRICHLET", "MHA_BC_NEUMANN"),
+    ("linearelasticity", 2, "BC_INTERFACE", "the interface condition (MHA_BC_INTERFACE) is not built"),
+    ("helmholtz", 2, "BC_WEAK_DIRICHLET", "MHA_BC_NEUMANN"),
+]
+
+
+@pytest.mark.parametrize("physics,nvars,bc,text", LATE_MODULE_CASES)
+def test_group_added_before_its_module_is_selected_is_refused_at_assembly(oracle, physics, nvars, bc, text):
+    """A block without a module takes any valid group; the module selected afterwards does not take this one.
+    assemble_boundary refuses it before anything is launched or written, naming the module and the group."""
+    torch = _torch()
+    import mrhyde_amd
+    from test_ns_thermal_gpu import _untouched_after
+    dim, ncell = 2, (2, 2)
+    m = oracle.mesh_multi(dim, ncell, [oracle.HGRAD] * nvars, [1] * nvars)
+    blk = mrhyde_amd.Block(dim, quadrature=2, physics=None, variables=[(oracle.HGRAD, 1)] * nvars)
+    blk.set_mesh(m["nodes"], m["lids"], m["offsets"], m["ndof"], None)
+    blk.set_orientation(m["orient"])
+    blk.set_graph()
+    be, bs = oracle.boundary_sides(dim, ncell, "left")
+    blk.add_boundary_group("left", getattr(mrhyde_amd, bc), be, bs)
+    assert blk.num_boundary_groups() == 1
+    assert mrhyde_amd.load_library().mha_physics_select(blk._h, mrhyde_amd.ALL_PHYSICS_IDS[physics]) == 0
+    ud = torch.zeros(m["ndof"], dtype=torch.float64, device="cuda")
+    msg = _untouched_after(lambda r, v: blk.assemble_boundary(ud, r, v), m["ndof"], len(blk.get_graph()[1]))
+    assert text in msg and physics + ":" in msg and "'left'" in msg
+
+
+def test_a_refused_select_leaves_the_block_as_it_was(oracle):
+    """An id that is no module, and a module that does not take the block's variables: both refused, and the block goes
+    on assembling with the module it had, on the path it took before."""
+    torch = _torch()
+    import mrhyde_amd
+    lib = mrhyde_amd.load_library()
+    m = oracle.mesh_structured(2, 1, (3, 3))
+    blk = make_block(m, 2, 1, 2)
+    blk.set_function("thermal source", 2.0)
+    rng = np.random.default_rng(11)
+    ud = torch.tensor(rng.uniform(-1, 1, m["ndof"]), device="cuda")
+    nnz = len(blk.get_graph()[1])
+
+    def assemble():
+        res = torch.zeros(m["ndof"], dtype=torch.float64, device="cuda")
+        vals = torch.zeros(nnz, dtype=torch.float64, device="cuda")
+        blk.assemble_jacres(ud, res, vals)
+        torch.cuda.synchronize()
+        return res.cpu().numpy(), vals.cpu().numpy(), blk.info("last_path")
+
+    res0, vals0, path0 = assemble()
+    for pid, text in ((99, "unknown physics module id 99"), (mrhyde_amd.ALL_PHYSICS_IDS["porousMixed"], "p (HVOL) and u (HDIV)"),
+                      (mrhyde_amd.ALL_PHYSICS_IDS["helmholtz"], "ureal, uimag")):
+        assert lib.mha_physics_select(blk._h, pid) == 1 and text in lib.mha_last_error().decode()
+        res1, vals1, path1 = assemble()
+        assert path1 == path0 and rel_err(res1, res0) < 1e-14 and rel_err(vals1, vals0) < 1e-14
