@@ -340,8 +340,8 @@ int mha_apply_mass_matrix_free(mha_context *ctx, int mode, const double *masswts
  * the refusals of the modules' own validation (e.g. a deck string that reads solution fields on a module without that
  * form).  A refused call writes nothing to y.  No allocation and no host synchronisation (beyond mha_set_timing's).
  * diag(A): mha_jacobian_diagonal; several vectors per call: mha_apply_jacobian_multi (below).
- * Not built: boundary-group terms (mha_assemble_boundary stays the way to get them: add that small matrix's product),
- * block diagonals, the HDG element / trace blocks, the wiring into the Newton driver.                                */
+ * Boundary-group terms: mha_apply_boundary_jacobian on the same y, after this call (below).
+ * Not built: block diagonals, the HDG element / trace blocks, the wiring into the Newton driver.                     */
 #define MHA_APPLY_TRANSPOSE 32
 int mha_apply_jacobian(mha_context *ctx, int flags, const double *u_dev, const double *u_prev_dev,
                        const double *u_stage_dev, const double *x_dev, double *y_dev);
@@ -355,7 +355,7 @@ int mha_apply_jacobian(mha_context *ctx, int flags, const double *u_dev, const d
  * those a value of their own.  flags: MHA_ASSEMBLE_OVERWRITE only (d is zeroed on the block's stream first; otherwise
  * accumulated into); any other bit, a missing mesh / module / graph, a null d and the refusals of the modules' own
  * validation give MHA_ERR_INVALID with d untouched.  No allocation and no host synchronisation.  The reference has no
- * counterpart.  Not built: block diagonals, boundary-group terms.                                                    */
+ * counterpart.  Boundary-group terms: mha_boundary_jacobian_diagonal on the same d.  Not built: block diagonals.       */
 int mha_jacobian_diagonal(mha_context *ctx, int flags, const double *u_dev, const double *u_prev_dev,
                           const double *u_stage_dev, double *d_dev);
 /* Y_k (+)= A X_k or, with MHA_APPLY_TRANSPOSE, A^T X_k for k = 0 .. nvec-1 with the matrix A and the flags of
@@ -372,6 +372,31 @@ int mha_jacobian_diagonal(mha_context *ctx, int flags, const double *u_dev, cons
 int mha_apply_jacobian_multi(mha_context *ctx, int flags, const double *u_dev, const double *u_prev_dev,
                              const double *u_stage_dev, int nvec, const double *x_dev, int64_t ldx,
                              double *y_dev, int64_t ldy);
+/* ---- matrix-free boundary-group products ---------------------------------------------------------------------------
+ * y_dev += A_b x_dev or, with MHA_APPLY_TRANSPOSE, y_dev += A_b^T x_dev, and d_dev += diag(A_b), where A_b is exactly the
+ * matrix that mha_assemble_boundary(ctx, MHA_ASSEMBLE_JACOBIAN, ...) adds into crs_vals: summed over the block's groups,
+ * the same sign and alpha_u seeding, zero rows where the mesh marks a row fixed.  Neither A_b nor an entry matrix is
+ * formed and the CRS graph is not read (it must be set, as for mha_assemble_boundary): per (element, side) entry the
+ * module's point form between (variable, slot) pairs is applied to the trial fields at the side points
+ * (kernels/boundary_forms.hpp, kernels/boundary_apply.hip) -- O(n nqs) work and n atomics per entry where the assembly
+ * takes O(n^2 nqs), n^2 atomics and a column search.  The calls always accumulate, as mha_assemble_boundary does: run
+ * mha_apply_jacobian(MHA_ASSEMBLE_OVERWRITE) first and this call on the same y for the operator of the whole problem.
+ * The forward product does not touch fixed rows of y, the transposed product reads x as zero on fixed rows, the diagonal
+ * adds nothing on fixed rows.  Groups with a Jacobian: thermal MHA_BC_WEAK_DIRICHLET / _INTERFACE, linearelasticity
+ * MHA_BC_WEAK_DIRICHLET, helmholtz MHA_BC_NEUMANN (Robin), shallowwaterHybridized MHA_BC_SWH_*.  Every other group
+ * (Neumann data, porousMixed, the thermoelastic traction, flux and strong-Dirichlet groups, cdr) is passed over without a
+ * launch; a block without groups returns MHA_OK with the output untouched.  flags: MHA_APPLY_TRANSPOSE for the product, 0
+ * for the diagonal; any other bit (MHA_ASSEMBLE_OVERWRITE and MHA_ASSEMBLE_DETERMINISTIC among them) and a null x, y or d
+ * give MHA_ERR_INVALID.  Everything mha_assemble_boundary refuses is refused here -- a missing mesh / module / graph, a
+ * group the module has no term for (with the group's name), the module's own validation, the kernel's limits -- before
+ * anything is written.  No allocation and no host synchronisation (beyond mha_set_timing's).  mha_get_info
+ * "boundary_apply_lds_bytes": LDS per workgroup of the largest launch of the last call.
+ * Not built: several vectors per call, the wiring into the Newton driver, the HDG element / trace blocks, a
+ * deterministic variant.                                                                                              */
+int mha_apply_boundary_jacobian(mha_context *ctx, int flags, const double *u_dev, const double *u_prev_dev,
+                                const double *u_stage_dev, const double *x_dev, double *y_dev);
+int mha_boundary_jacobian_diagonal(mha_context *ctx, int flags, const double *u_dev, const double *u_prev_dev,
+                                   const double *u_stage_dev, double *d_dev);
 /* replaces: scatterJac / scatterRes  assemblyManager.cpp:3882-3935, 3943-3978          */
 int mha_scatter_local(mha_context *ctx, const double *local_J_dev, const double *local_res_dev,
                       double *res_dev, double *crs_vals_dev);

@@ -33,7 +33,8 @@ EXPORTS = [
     "mha_kl_indices", "mha_swhdg_set_subgrids", "mha_swhdg_condensed_subgrid", "mha_swhdg_subgrid_blocks",
     "mha_mesh_swhdg_subgrids_sizes", "mha_mesh_swhdg_subgrids",
     "mha_num_derived", "mha_derived_name", "mha_get_derived_values", "mha_apply_jacobian",
-    "mha_jacobian_diagonal", "mha_apply_jacobian_multi",
+    "mha_jacobian_diagonal", "mha_apply_jacobian_multi", "mha_apply_boundary_jacobian",
+    "mha_boundary_jacobian_diagonal",
 ]
 KL_MAX_TERMS = 8  # MHA_KL_MAX_TERMS: KL roots per direction the kernels evaluate
 MASS_ON_THE_FLY, MASS_LOCAL, MASS_DATABASE, MASS_DATABASE_SPARSE = 0, 1, 2, 3
@@ -141,6 +142,8 @@ def load_library():
         _lib.mha_apply_mass_matrix_free.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         _lib.mha_apply_jacobian.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         _lib.mha_jacobian_diagonal.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+        _lib.mha_apply_boundary_jacobian.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        _lib.mha_boundary_jacobian_diagonal.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
         _lib.mha_apply_jacobian_multi.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [
             C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
         _lib.mha_num_boundary_groups.argtypes = [C.c_void_p]
@@ -875,6 +878,17 @@ class Block:
         zero where A is: on fixed rows and on rows the module leaves empty."""
         _check(load_library().mha_jacobian_diagonal(self._h, ASSEMBLE_OVERWRITE if overwrite else 0, _ptr(u), _ptr(u_prev),
                                                     _ptr(u_stage), _ptr(d)))
+
+    def apply_boundary_jacobian(self, u, x, y, transpose=False, u_prev=None, u_stage=None):
+        """y += A_b x (transpose: A_b^T x) with the matrix assemble_boundary adds into crs_vals -- all groups of the block,
+        current seeding, fixed rows zero -- never formed (mha_apply_boundary_jacobian).  Always accumulates: run
+        apply_jacobian(..., overwrite=True) first and this on the same y."""
+        _check(load_library().mha_apply_boundary_jacobian(self._h, APPLY_TRANSPOSE if transpose else 0, _ptr(u), _ptr(u_prev),
+                                                          _ptr(u_stage), _ptr(x), _ptr(y)))
+
+    def boundary_jacobian_diagonal(self, u, d, u_prev=None, u_stage=None):
+        """d += diag(A_b) with the matrix of apply_boundary_jacobian, never formed (mha_boundary_jacobian_diagonal)."""
+        _check(load_library().mha_boundary_jacobian_diagonal(self._h, 0, _ptr(u), _ptr(u_prev), _ptr(u_stage), _ptr(d)))
 
     def apply_jacobian_multi(self, u, X, Y, transpose=False, overwrite=False, u_prev=None, u_stage=None):
         """Y[k] += A X[k] (transpose: A^T X[k]; overwrite: Y[k] = ...) for every row k of X (mha_apply_jacobian_multi).

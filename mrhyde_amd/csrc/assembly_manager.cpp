@@ -890,6 +890,7 @@ struct ApplyRestore {  // a refusal inside the module leaves the workset as an a
   ~ApplyRestore() {
     w.apply.mode = 0;
     w.apply.nvec = 0;
+    w.apply.check_only = false;
     w.use_point_engine = false;
   }
 };
@@ -1605,6 +1606,28 @@ void AssemblyManager::setDirichlet(int lump_mass, double *rhs, double *mass_vals
   launch_free_row_identity(blockDev(), mass_vals, stream_);
 }
 
+// a group added before the module was selected, or whose side got data since: refused before anything is written
+void AssemblyManager::checkModuleGroups() const {
+  for (const auto &g : boundary_groups_) {
+    if (g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX) continue;
+    try {
+      checkModuleGroup(g->bc_type, g->sidename);
+    } catch (const Error &e) {
+      throw Error(e.code, std::string(e.what()) + " (group '" + g->sidename + "')");
+    }
+  }
+}
+
+// updateWorksetBoundary (assemblyManager.cpp:5646-5710): the workset's boundary state for a group of the modules
+void AssemblyManager::bindBoundaryGroup(const BoundaryGroupData &g) {
+  wkset_.sidename = g.sidename;
+  wkset_.current_bc = g.bc_type;
+  wkset_.bnd = boundaryDev(g);
+  wkset_.side_tables = sideTablesDev();
+  wkset_.layout = layout_;
+  wkset_.layout.orient = has_orient_ ? d_orient_.data() : nullptr;
+}
+
 // reference: the boundary-group loop of assembleJacRes (assemblyManager.cpp:2518-2638): per group
 // updateWorksetBoundary, performBoundaryGather, physics boundaryResidual, scatter.  Accumulates.
 void AssemblyManager::assembleBoundary(int flags, const double *u, const double *u_prev, const double *u_stage,
@@ -1616,15 +1639,7 @@ void AssemblyManager::assembleBoundary(int flags, const double *u, const double 
   MHA_REQUIRE(res != nullptr, MHA_ERR_INVALID, "residual vector is null");
   MHA_REQUIRE(!compute_jacobian || crs_vals, MHA_ERR_INVALID, "compute_jacobian set but crs_vals is null");
   bindState(u, u_prev, u_stage);
-  // a group added before the module was selected, or whose side got data since: refused before anything is written
-  for (const auto &g : boundary_groups_) {
-    if (g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX) continue;
-    try {
-      checkModuleGroup(g->bc_type, g->sidename);
-    } catch (const Error &e) {
-      throw Error(e.code, std::string(e.what()) + " (group '" + g->sidename + "')");
-    }
-  }
+  checkModuleGroups();
   timedBegin();
   for (size_t gi = 0; gi < boundary_groups_.size(); ++gi) {
     const auto &g = boundary_groups_[gi];
@@ -1641,12 +1656,7 @@ void AssemblyManager::assembleBoundary(int flags, const double *u, const double 
                             varComps(g->var), g->wts.data(), xyz, nrm, basis, res, stream_);
       continue;
     }
-    wkset_.sidename = g->sidename;
-    wkset_.current_bc = g->bc_type;
-    wkset_.bnd = boundaryDev(*g);
-    wkset_.side_tables = sideTablesDev();
-    wkset_.layout = layout_;
-    wkset_.layout.orient = has_orient_ ? d_orient_.data() : nullptr;
+    bindBoundaryGroup(*g);
     wkset_.res = ElemOut();
     wkset_.res.compute_jacobian = compute_jacobian;
     wkset_.res.res = res;
@@ -1654,6 +1664,55 @@ void AssemblyManager::assembleBoundary(int flags, const double *u, const double 
     physics_->boundaryResidual();
   }
   timedEnd();
+}
+
+// y += A_b x / A_b^T x (mode 1 / 2) or y += diag(A_b) (mode 3), A_b the matrix assembleBoundary(MHA_ASSEMBLE_JACOBIAN)
+// adds into crs_vals, summed over the groups: assembleBoundary's loop with the request in wkset_.apply, so that each
+// module's boundaryResidual launches the product kernel (kernels/boundary_apply.hip) on the device record it builds for
+// the assembly.  Groups without a Jacobian (flux and strong-Dirichlet groups, data-only types) add nothing.  The loop runs
+// twice: the first pass makes every refusal -- the modules' validation and the kernel's limits -- and launches nothing,
+// so a refused call has written nothing.  The reference has no counterpart.
+void AssemblyManager::boundaryProduct(int mode, const double *u, const double *u_prev, const double *u_stage,
+                                      const double *x, double *y) {
+  requireReady(true);
+  MHA_REQUIRE(y && (mode == 3 || x), MHA_ERR_INVALID, "null vector");
+  bindState(u, u_prev, u_stage);
+  checkModuleGroups();
+  wkset_.apply.mode = mode;
+  wkset_.apply.overwrite = 0;
+  wkset_.apply.x = x;
+  wkset_.apply.y = y;
+  wkset_.apply.nvec = 0;
+  wkset_.apply.bnd_lds_bytes = 0;
+  ApplyRestore restore{wkset_};
+  timedBegin();
+  for (int pass = 0; pass < 2; ++pass) {
+    wkset_.apply.check_only = pass == 0;
+    for (const auto &g : boundary_groups_) {
+      if (g->bc_type == MHA_BC_DIRICHLET || g->bc_type == MHA_BC_FLUX) continue;
+      bindBoundaryGroup(*g);
+      wkset_.res = ElemOut();
+      physics_->boundaryResidual();
+    }
+  }
+  timedEnd();
+}
+
+void AssemblyManager::applyBoundaryJacobian(int flags, const double *u, const double *u_prev, const double *u_stage,
+                                            const double *x, double *y) {
+  MHA_REQUIRE(!(flags & MHA_ASSEMBLE_OVERWRITE), MHA_ERR_INVALID,
+              "boundary terms are accumulated after the volume terms: MHA_ASSEMBLE_OVERWRITE is not valid here");
+  MHA_REQUIRE((flags & ~MHA_APPLY_TRANSPOSE) == 0, MHA_ERR_INVALID,
+              "mha_apply_boundary_jacobian takes MHA_APPLY_TRANSPOSE only (flags " << flags << ")");
+  boundaryProduct((flags & MHA_APPLY_TRANSPOSE) ? 2 : 1, u, u_prev, u_stage, x, y);
+}
+
+void AssemblyManager::boundaryJacobianDiagonal(int flags, const double *u, const double *u_prev, const double *u_stage,
+                                               double *d) {
+  MHA_REQUIRE(!(flags & MHA_ASSEMBLE_OVERWRITE), MHA_ERR_INVALID,
+              "boundary terms are accumulated after the volume terms: MHA_ASSEMBLE_OVERWRITE is not valid here");
+  MHA_REQUIRE(flags == 0, MHA_ERR_INVALID, "mha_boundary_jacobian_diagonal takes no flags (flags " << flags << ")");
+  boundaryProduct(3, u, u_prev, u_stage, nullptr, d);
 }
 
 const char *AssemblyManager::derivedName(int k) {
@@ -2264,6 +2323,7 @@ int64_t AssemblyManager::info(const std::string &key) const {
   if (key == "jacobian_apply_vectors") return wkset_.apply.vectors;  // last mha_apply_jacobian_multi: vectors per launch (Kc)
   if (key == "jacobian_diag_lds_bytes") return static_cast<int64_t>(wkset_.apply.diag_lds_bytes);  // last mha_jacobian_diagonal
   if (key == "jacobian_diag_waves") return wkset_.apply.diag_waves;
+  if (key == "boundary_apply_lds_bytes") return static_cast<int64_t>(wkset_.apply.bnd_lds_bytes);  // last boundary-group product: largest launch
   if (key == "jacobian_database_mode") return last_db_mode_;  // the last affine row-owner Jacobian replicated one block per pattern
   if (key == "block_pattern_rep_launches") return rep_launches_;  // representative launches of the geometry-database mode so far
   if (key == "affine_shapes") return ro_.ready ? ro_.k1_plan.num_shapes : 0;  // distinct geometry records behind the residual kernel's database index

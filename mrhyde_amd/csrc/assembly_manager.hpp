@@ -96,6 +96,11 @@ class AssemblyManager {
   int numBoundaryGroups() const { return static_cast<int>(boundary_groups_.size()); }
   void assembleBoundary(int flags, const double *u, const double *u_prev, const double *u_stage, double *res,
                         double *crs_vals);
+  // y += A_b x / A_b^T x and d += diag(A_b) with the matrix A_b that assembleBoundary(MHA_ASSEMBLE_JACOBIAN) adds into
+  // crs_vals, never formed (kernels/boundary_apply.hip); flags: MHA_APPLY_TRANSPOSE for the product, none for the diagonal
+  void applyBoundaryJacobian(int flags, const double *u, const double *u_prev, const double *u_stage, const double *x,
+                             double *y);
+  void boundaryJacobianDiagonal(int flags, const double *u, const double *u_prev, const double *u_stage, double *d);
   // <module>::getDerivedNames / getDerivedValues (linearelasticity.cpp:1289-1360) on all elements of the block
   int numDerived() const { return physics_ ? static_cast<int>(physics_->getDerivedNames().size()) : 0; }
   const char *derivedName(int k);
@@ -338,6 +343,9 @@ class AssemblyManager {
   BoundaryDev boundaryDev(const BoundaryGroupData &g) const;
   // the selected module's rule for a group of the modules (PhysicsBase::checkBoundaryGroup), the default one without a module
   void checkModuleGroup(int bc_type, const std::string &sidename) const;
+  void checkModuleGroups() const;
+  void bindBoundaryGroup(const BoundaryGroupData &g);
+  void boundaryProduct(int mode, const double *u, const double *u_prev, const double *u_stage, const double *x, double *y);
 
   // scratch of the two-step (updateJac/scatterJac) path, one workset wide
   DeviceBuffer<double> d_local_J_, d_local_res_;

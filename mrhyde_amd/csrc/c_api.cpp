@@ -786,6 +786,16 @@ int mha_apply_jacobian_multi(mha_context *ctx, int flags, const double *u_dev, c
   });
 }
 
+int mha_apply_boundary_jacobian(mha_context *ctx, int flags, const double *u_dev, const double *u_prev_dev,
+                                const double *u_stage_dev, const double *x_dev, double *y_dev) {
+  return guarded([&] { mgr(ctx).applyBoundaryJacobian(flags, u_dev, u_prev_dev, u_stage_dev, x_dev, y_dev); });
+}
+
+int mha_boundary_jacobian_diagonal(mha_context *ctx, int flags, const double *u_dev, const double *u_prev_dev,
+                                   const double *u_stage_dev, double *d_dev) {
+  return guarded([&] { mgr(ctx).boundaryJacobianDiagonal(flags, u_dev, u_prev_dev, u_stage_dev, d_dev); });
+}
+
 int mha_scatter_plan_create(int n, int64_t num_elems, int64_t num_rows, const int32_t *lids_host,
                             const int32_t *rowptr_host, const int32_t *colind_host, const uint8_t *fixed_host,
                             mha_scatter_plan **out) {

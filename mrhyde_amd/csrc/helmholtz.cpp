@@ -104,7 +104,8 @@ void helmholtz::boundaryResidual() {
   }
   BoundaryDev bd = w.bnd;
   bd.bc_type = w.current_bc;
-  launch_helmholtz_boundary(w.dev, w.side_tables, bd, hb, w.time_dev, w.res, w.stream);
+  if (w.apply.mode) launch_boundary_apply(w.dev, w.side_tables, bd, hb, w.time_dev, w.boundaryRequest(), w.stream);
+  else launch_helmholtz_boundary(w.dev, w.side_tables, bd, hb, w.time_dev, w.res, w.stream);
 }
 
 // helmholtz::computeFlux is empty (helmholtz.cpp:430-433): the flux view keeps the zeros the workset reset left in it

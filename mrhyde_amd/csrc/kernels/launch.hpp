@@ -154,6 +154,28 @@ bool helmholtz_boundary_supported(int dim, int n, int nqs);
 void launch_helmholtz_boundary(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd,
                                const HelmholtzBoundaryDev &hb, const TimeDev &tm, const ElemOut &out, hipStream_t stream);
 
+// boundary_apply.hip: y += A_b x (mode 1), y += A_b^T x (mode 2), y += diag(A_b) (mode 3) with the matrix A_b that the
+// group's assembly kernel above adds into the CRS values, from the module's point form (boundary_forms.hpp): no matrix,
+// no CRS graph.  One overload per device record of the modules.  A group whose type has no Jacobian returns without a
+// launch; what does not fit the kernel is refused with MHA_ERR_INVALID.  check_only: the refusals alone, nothing is
+// launched.  lds_bytes (may be null): raised to the launch's LDS per workgroup where that is larger
+struct BoundaryApplyRequest {
+  int mode = 0;
+  const double *x = nullptr;
+  double *y = nullptr;
+  bool check_only = false;
+  size_t *lds_bytes = nullptr;
+};
+void launch_boundary_apply(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd, const TimeDev &tm,
+                           const BoundaryApplyRequest &rq, hipStream_t stream);  // thermal
+void launch_boundary_apply(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd, const LeBoundaryDev &le,
+                           const TimeDev &tm, const BoundaryApplyRequest &rq, hipStream_t stream);
+void launch_boundary_apply(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd,
+                           const HelmholtzBoundaryDev &hb, const TimeDev &tm, const BoundaryApplyRequest &rq,
+                           hipStream_t stream);
+void launch_boundary_apply(const BlockDev &b, const SideTablesDev &st, const BoundaryDev &bd, const SwhBoundaryDev &sw,
+                           const TimeDev &tm, const BoundaryApplyRequest &rq, hipStream_t stream);
+
 // linearelasticity_stress.hip: linearelasticity::getDerivedValues (stress tensor, "VM stress", "MAG stress")
 void launch_linearelasticity_stress(const BlockDev &b, const LeStressDev &a, hipStream_t stream);
 

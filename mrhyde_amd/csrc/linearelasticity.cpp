@@ -107,7 +107,8 @@ void linearelasticity::boundaryResidual() {
   le.plane_stress = incplanestress && dim == 2 ? 1 : 0;
   BoundaryDev bd = w.bnd;
   bd.bc_type = w.current_bc;
-  launch_linearelasticity_boundary(w.dev, w.side_tables, bd, le, w.time_dev, w.res, w.stream);
+  if (w.apply.mode) launch_boundary_apply(w.dev, w.side_tables, bd, le, w.time_dev, w.boundaryRequest(), w.stream);
+  else launch_linearelasticity_boundary(w.dev, w.side_tables, bd, le, w.time_dev, w.res, w.stream);
 }
 
 void linearelasticity::computeFlux() {
@@ -209,7 +210,8 @@ void linearelasticityThermal::boundaryResidual() {
   le.disp_card = w.layout.card[0];
   BoundaryDev bd = w.bnd;
   bd.bc_type = w.current_bc;
-  launch_linearelasticity_boundary(w.dev, w.side_tables, bd, le, w.time_dev, w.res, w.stream);
+  if (w.apply.mode) launch_boundary_apply(w.dev, w.side_tables, bd, le, w.time_dev, w.boundaryRequest(), w.stream);
+  else launch_linearelasticity_boundary(w.dev, w.side_tables, bd, le, w.time_dev, w.res, w.stream);
 }
 
 void linearelasticityThermal::computeFlux() {

@@ -201,7 +201,8 @@ void thermal::boundaryResidual() {
   } else {
     return;  // strong Dirichlet / none: no boundary term (thermal.cpp:188-216 falls through)
   }
-  launch_thermal_boundary(w.dev, w.side_tables, bd, w.time_dev, w.res, w.stream);
+  if (w.apply.mode) launch_boundary_apply(w.dev, w.side_tables, bd, w.time_dev, w.boundaryRequest(), w.stream);
+  else launch_thermal_boundary(w.dev, w.side_tables, bd, w.time_dev, w.res, w.stream);
 }
 
 // reference: thermal<EvalT>::computeFlux (src/physics/thermal.cpp:288-347): wkset->flux(elem, e, pt) on the current
@@ -380,6 +381,7 @@ void porousMixed::boundaryResidual() {
   BoundaryDev bd = w.bnd;
   bd.bc_type = w.current_bc;
   bd.data = functionManager->evaluate("Dirichlet p " + w.sidename);
+  if (w.apply.mode) return;  // data on the u rows: no Jacobian, nothing for a boundary-group product
   launch_porous_boundary(w.dev, w.side_tables, bd, w.layout, w.res, w.stream);
 }
 
@@ -574,7 +576,8 @@ void shallowwaterHybridized::boundaryResidual() {
     else
       sw.farfield[i] = sw.aux[i];
   }
-  launch_swhdg_boundary(w.dev, w.side_tables, w.bnd, sw, w.time_dev, w.res, w.stream);
+  if (w.apply.mode) launch_boundary_apply(w.dev, w.side_tables, w.bnd, sw, w.time_dev, w.boundaryRequest(), w.stream);
+  else launch_swhdg_boundary(w.dev, w.side_tables, w.bnd, sw, w.time_dev, w.res, w.stream);
 }
 
 std::unique_ptr<PhysicsBase> import_physics(int physics_id, int dim) {

@@ -56,7 +56,9 @@ class Workset {
   // matrix-free Jacobian requests: mode != 0 sends the module's volume terms to them instead of the element assembly.
   // 1: y (+)= A x, 2: y (+)= A^T x (kernels/jacobian_apply.hip; with nvec >= 1 the vectors x + k ldx -> y + k ldy,
   // kernels/jacobian_apply_multi.hip), 3: y (+)= diag(A) (kernels/jacobian_diagonal.hip).  lds_bytes / waves / vectors
-  // report the last product's launch, diag_* the last diagonal's
+  // report the last product's launch, diag_* the last diagonal's.  The boundary-group products (mha_apply_boundary_jacobian,
+  // mha_boundary_jacobian_diagonal) put the same request here for the modules' boundaryResidual (kernels/boundary_apply.hip);
+  // check_only: their first pass over the groups, refusals alone; bnd_lds_bytes: the largest launch of the last such call
   struct Apply {
     int mode = 0, overwrite = 0;
     const double *x = nullptr;
@@ -65,7 +67,10 @@ class Workset {
     int64_t ldx = 0, ldy = 0;
     size_t lds_bytes = 0, diag_lds_bytes = 0;
     int waves = 0, vectors = 0, diag_waves = 0;
+    bool check_only = false;
+    size_t bnd_lds_bytes = 0;
   } apply;
+  BoundaryApplyRequest boundaryRequest() { return {apply.mode, apply.x, apply.y, apply.check_only, &apply.bnd_lds_bytes}; }
   bool single_hgrad = true;  // basis / basis_grad views exist for single-variable HGRAD blocks only
   hipStream_t stream = nullptr;
   int order = 0, nq1 = 0;
