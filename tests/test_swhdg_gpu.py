@@ -265,6 +265,7 @@ def test_batched_condensation(oracle):
     import mrhyde_amd
     from test_multi_gpu import make_block, transient_state
     from test_oracle_swhdg import hdg_case
+    from highprec_swhdg_ref import condense_longdouble
     rng = np.random.default_rng(71)
 
     def check(blocks, res, ni, nt):
@@ -283,26 +284,6 @@ def test_batched_condensation(oracle):
             print("condense (%d, %d) %s: %.3e (bound 1e-10), row exchanges per element >= %d" % (ni, nt, name, err, nswap))
             assert err < 1e-10, (ni, nt, name)
         return nswap
-
-    def condense_longdouble(blocks, res, ni, nt):
-        E, n = res.shape
-        M = np.concatenate([blocks[:, :ni, :], res[:, :ni, None]], axis=2).astype(np.longdouble)  # [E][ni][n + 1]
-        ar = np.arange(E)
-        nswap = np.zeros(E, dtype=int)
-        for k in range(ni):
-            piv = k + np.argmax(np.abs(M[:, k:, k]), axis=1)
-            nswap += piv != k
-            rk, rp = M[ar, k].copy(), M[ar, piv].copy()
-            M[ar, piv], M[ar, k] = rk, rp
-            M[:, k] = M[:, k] / M[:, k, k:k + 1]
-            f = M[:, :, k].copy()
-            f[:, k] = 0
-            M = M - f[:, :, None] * M[:, k:k + 1, :]
-        X = M[:, :, ni:]                                                                          # [X_ul | x_r]
-        low = np.concatenate([blocks[:, ni:, :], res[:, ni:, None]], axis=2).astype(np.longdouble)
-        Sg = low[:, :, ni:] - np.einsum("eai,eib->eab", low[:, :, :ni], X)
-        return (Sg[:, :, :nt].astype(np.float64), Sg[:, :, nt].astype(np.float64), X[:, :, nt].astype(np.float64),
-                int(nswap.min()))
 
     # (5, 40), (30, 33), (1, 62): more than kCondMaxTrace = 32 trace rows, the loop of condense.hip that re-reads them
     for ni, nt in ((12, 24), (5, 3), (32, 31), (1, 1), (5, 40), (30, 33), (1, 62)):
