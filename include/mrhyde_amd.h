@@ -199,6 +199,27 @@ int mha_get_graph(mha_context *ctx, int32_t *rowptr_host, int32_t *colind_host);
  * strings that read the solution fields, weak-Dirichlet and interface groups, and any of the ten volume functions given
  * as a volume MHA_FUNC_IP_ARRAY while a Neumann group exists.                                                        */
 #define MHA_PHYSICS_HELMHOLTZ (MHA_PHYSICS_LINEARELASTICITY_THERMAL + 3)
+/* porousMixedHybridized, hybridized mixed Darcy flow (src/physics/porousMixedHybridized.cpp; the reference's label is
+ * "porousMixedHybrid", the deck's module name "porous mixed hybridized"): p (HVOL 0), u (HDIV-DG 1) and the trace lambda
+ * (HFACE 0) of :20-41.  The BLOCK holds p and u, in that order, on 2-D quads and 3-D hexes; lambda, one constant per
+ * face, is no block variable: as with shallowwaterHybridized it arrives as data per element, lambda[E][2 dim], and its
+ * rows live in the caller's trace system.  The block's LIDs are DG: every LID belongs to exactly one element (checked on
+ * the host by the element step, once per mesh; a conforming HDIV map is refused).  Functions (:54-66): "source" (0),
+ * "Kinv_xx", "Kinv_yy", "Kinv_zz" (1): constants, arrays, closed forms or deck strings in the coordinates.  Parameter
+ * "use permeability data" (:42): Kinv_xx = Kinv_yy = Kinv_zz = 1 / data(elem, 0) of the block's element data, as on
+ * porousMixed.  volumeResidual (:72-189) is porousMixed's with total_mobility == 1 and runs on porousMixed's point
+ * function with that function pinned to the constant 1: mha_assemble_jacres, mha_compute_local_jacres,
+ * mha_apply_jacobian, mha_jacobian_diagonal, mha_get_mass and the workset views (p, u[x], div(u)) work on the block.
+ * faceResidual (:287-362, `assemble face terms: true`) on all 2 dim faces of every element is the element step
+ * mha_pmh_element_blocks / mha_pmh_condensed_element below.  Dirichlet data enters as the decks give it, `Dirichlet
+ * conditions: lambda`: the caller fixes the trace rows (mha_scatter_plan_create, fixed_host) and puts the values into
+ * lambda; the step is a Newton residual at the given state, so non-zero data lifts itself.  Refused with
+ * MHA_ERR_INVALID: the KL options of porousMixed (the reference module has none), deck strings that read the solution
+ * fields, boundary groups of the module (the weak "Dirichlet p" and "interface" branches of boundaryResidual :196-280),
+ * mha_compute_flux (:369-408), 1-D, MHA_ASSEMBLE_DETERMINISTIC, a transient state in the element step.  Not built: HDIV
+ * or HFACE above lowest order, triangles and tetrahedra, the multiscale interface / "aux p" coupling.                  */
+/* (id 12: + 4 stays unassigned, the module-rule tests pin 11 as an id that names no module) */
+#define MHA_PHYSICS_POROUS_MIXED_HYBRIDIZED (MHA_PHYSICS_LINEARELASTICITY_THERMAL + 5)
 int mha_physics_select(mha_context *ctx, int physics_id);
 #define MHA_FUNC_CONSTANT 0
 #define MHA_FUNC_IP_ARRAY 1     /* dev pointer to [E][numip] f64                    */
@@ -751,6 +772,45 @@ int mha_swhdg_subgrid_blocks(mha_context *ctx, const double *u_dev, const double
 int mha_mesh_swhdg_subgrids_sizes(const int *ncell_macro, int m, int *nelem, int64_t *ndof, int64_t *ntrace);
 int mha_mesh_swhdg_subgrids(const int *ncell_macro, int m, const double *lo, const double *hi, double *nodes,
                             int32_t *lids, int32_t *offsets, int32_t *trace_lids);
+/* ---- porousMixedHybridized: the element step --------------------------------------------------------------------
+ * replaces: porousMixedHybrid::volumeResidual + faceResidual (src/physics/porousMixedHybridized.cpp:72-189, 287-362) on
+ * every element and all of its 2 dim faces, in the layout and conventions of the shallowwaterHybridized entry points
+ * above.  Unknowns of an element: the interior ones first -- p, then the 2 dim flux dofs in (variable, dof) order, dof
+ * 2 c + s = the face of direction c on the low (s = 0) or high (s = 1) side -- then the 2 dim traces in the reference's
+ * HFACE order: left x=-1, bottom y=-1, right x=+1, top y=+1 for quads (src/tools/Intrepid2_HFACE_QUAD_In_FEMdef.hpp),
+ * then front z=-1, back z=+1 for hexes (src/tools/Intrepid2_HFACE_HEX_In_FEMdef.hpp:97-269).  n_int = 1 + 2 dim,
+ * n = n_int + 2 dim.  With the block's quadrature in the volume and the side points of the side tables:
+ *   R_u = int (Kinv u) . v - p div v + sum_faces int_F lambda v . n,   R_p = int (-div u + source) q,
+ *   R_lambda = - sum_faces int_F (u . n) mu.
+ * u_dev[nrows] is the block's state (steady; a transient context is refused), lambda_dev[E][2 dim] the traces.
+ * mha_pmh_element_blocks: res_dev[E][n] = -res.val(), blocks_dev[E][n][n] = d res / d unknown (either may be NULL), by a
+ * plain kernel, one thread per (element, row): the implementation the fused kernel is compared with, through
+ * mha_batched_condense.  The p-lambda, lambda-lambda and p-p entries are exactly 0.0.
+ * mha_pmh_condensed_element: geometry, local matrices, interior solve and Schur complement in one launch, one thread per
+ * element; schur_dev[E][2 dim][2 dim], gvec_dev[E][2 dim], du_dev[E][n_int] as mha_batched_condense defines them (any may
+ * be NULL, not all) are all that is written, in whole 16-byte pieces that are contiguous across a wavefront.  It uses
+ * the structure instead of a pivoted dense solve: A = (Kinv phi_i, phi_j) is symmetric positive definite (Cholesky),
+ * the p unknown has the scalar Schur complement B A^-1 B^T > 0, the trace coupling is one entry per face.  A
+ * non-positive pivot (degenerate element, Kinv <= 0) is counted into *num_singular_dev (device counter, may be NULL;
+ * an integer atomic that runs for such elements only); that element's outputs are unspecified but finite.  Enqueued on
+ * the context's stream: no host synchronisation, no allocation (side tables and the DG check are made on the first call
+ * after mha_set_mesh).  No floating-point atomics: two runs are bit-identical.
+ * The linear solve on one block is two calls: step at (u, lambda); mha_scatter_plan_apply(schur, gvec) with the boundary
+ * trace rows fixed; the caller solves the trace system and updates lambda; step again and u += du.  The second call's
+ * gvec is zero to round-off on free rows.                                                                            */
+int mha_pmh_element_blocks(mha_context *ctx, const double *u_dev, const double *lambda_dev, double *res_dev,
+                           double *blocks_dev);
+int mha_pmh_condensed_element(mha_context *ctx, const double *u_dev, const double *lambda_dev, double *schur_dev,
+                              double *gvec_dev, double *du_dev, int32_t *num_singular_dev);
+/* Mesh helper (input generation, host only): ncell[dim] cells on [lo, hi], dim = 2 or 3, for a porousMixedHybridized
+ * block.  sizes: nelem, ndof = nelem (1 + 2 dim) DG unknowns, ntrace = faces of the mesh.  nodes[E][2^dim][dim] (shards
+ * vertex order), lids[E][1 + 2 dim] (every LID once), offsets[1 + 2 dim] and orient[E][1 + 2 dim] (the face signs
+ * mha_mesh_structured_multi gives conforming HDIV) for mha_set_mesh / mha_set_orientation; trace_lids[E][2 dim] in the
+ * HFACE face order above for mha_scatter_plan_create; trace_side[ntrace] u8: 0 for an interior face, 1 + side on the
+ * boundary with side 0 left (x low), 1 right, 2 bottom (y low), 3 top, 4 front (z low), 5 back.                       */
+int mha_mesh_porous_hybrid_sizes(int dim, const int *ncell, int *nelem, int64_t *ndof, int64_t *ntrace);
+int mha_mesh_porous_hybrid(int dim, const int *ncell, const double *lo, const double *hi, double *nodes, int32_t *lids,
+                           int32_t *offsets, int8_t *orient, int32_t *trace_lids, uint8_t *trace_side);
 /* Batched static condensation of element blocks: eliminates the n_int interior unknowns of every element.
  * replaces: the element-local direct solve of the subgrid solver and its forward sensitivities d u / d lambda
  * (SubGridDtN_Solver, src/subgrid/subgridDtN_solver.cpp:681-903, 1542-1616) in Schur-complement form.

@@ -35,6 +35,7 @@ EXPORTS = [
     "mha_num_derived", "mha_derived_name", "mha_get_derived_values", "mha_apply_jacobian",
     "mha_jacobian_diagonal", "mha_apply_jacobian_multi", "mha_apply_boundary_jacobian",
     "mha_boundary_jacobian_diagonal",
+    "mha_pmh_element_blocks", "mha_pmh_condensed_element", "mha_mesh_porous_hybrid_sizes", "mha_mesh_porous_hybrid",
 ]
 KL_MAX_TERMS = 8  # MHA_KL_MAX_TERMS: KL roots per direction the kernels evaluate
 MASS_ON_THE_FLY, MASS_LOCAL, MASS_DATABASE, MASS_DATABASE_SPARSE = 0, 1, 2, 3
@@ -59,6 +60,11 @@ PHYSICS_NAVIERSTOKES_CDR = 9
 # name up in ALL_PHYSICS_IDS, which holds every module.
 PHYSICS_HELMHOLTZ = 10
 ALL_PHYSICS_IDS = dict(PHYSICS_IDS, helmholtz=PHYSICS_HELMHOLTZ)
+# porousMixedHybridized: p (HVOL), u (HDIV-DG) on the block, the trace lambda (HFACE) as data per element.  Id 11 stays
+# unassigned (tests/test_module_rules.py pins it as an id that names no module, and ALL_PHYSICS_IDS as the table of the
+# ten modules before this one); Block looks a name up in MODULE_IDS, which holds every module.
+PHYSICS_POROUS_MIXED_HYBRIDIZED = 12
+MODULE_IDS = dict(ALL_PHYSICS_IDS, porousMixedHybridized=PHYSICS_POROUS_MIXED_HYBRIDIZED)
 PATH_POINT_ENGINE = 4
 PATH_ROW_GATHER = 5
 BC_NEUMANN, BC_WEAK_DIRICHLET, BC_FLUX = 1, 2, 3
@@ -170,6 +176,10 @@ def load_library():
         _lib.mha_swhdg_subgrid_blocks.argtypes = [C.c_void_p] * 9
         _lib.mha_mesh_swhdg_subgrids_sizes.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
         _lib.mha_mesh_swhdg_subgrids.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        _lib.mha_pmh_element_blocks.argtypes = [C.c_void_p] * 5
+        _lib.mha_pmh_condensed_element.argtypes = [C.c_void_p] * 7
+        _lib.mha_mesh_porous_hybrid_sizes.argtypes = [C.c_int] + [C.c_void_p] * 4
+        _lib.mha_mesh_porous_hybrid.argtypes = [C.c_int] + [C.c_void_p] * 9
     return _lib
 
 
@@ -498,6 +508,48 @@ def mesh_swhdg_subgrids(ncell_macro, m, lo=None, hi=None):
     return out
 
 
+PMH_SIDES = ("left", "right", "bottom", "top", "front", "back")  # trace_side - 1 of mesh_porous_hybrid
+
+
+def mesh_porous_hybrid(ncell, lo=None, hi=None):
+    """Mesh of a porousMixedHybridized block (mha_mesh_porous_hybrid): len(ncell) = 2 (quads) or 3 (hexes).
+    -> dict(nodes [E][2^dim][dim], lids [E][1+2dim] (DG), offsets, orient [E][1+2dim], trace_lids [E][2dim] (HFACE face
+    order: left, bottom, right, top[, front, back]), trace_side [ntrace] (0 interior, 1 + index into PMH_SIDES on the
+    boundary), ndof, ntrace, nelem, dim)."""
+    lib = load_library()
+    nc = _np(ncell, np.int32)
+    dim = len(nc)
+    lo = _np(np.zeros(dim) if lo is None else lo, np.float64)
+    hi = _np(np.ones(dim) if hi is None else hi, np.float64)
+    if dim not in (2, 3) or len(lo) != dim or len(hi) != dim:
+        raise ValueError("mesh_porous_hybrid: ncell, lo, hi of length 2 or 3")
+    ne, nd, nt = C.c_int(), C.c_int64(), C.c_int64()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(lib.mha_mesh_porous_hybrid_sizes(dim, vp(nc), C.byref(ne), C.byref(nd), C.byref(nt)))
+    ni, nu = 1 + 2 * dim, 2 * dim
+    out = dict(nodes=np.zeros((ne.value, 2 ** dim, dim)), lids=np.zeros((ne.value, ni), np.int32), offsets=np.zeros(ni, np.int32),
+               orient=np.ones((ne.value, ni), np.int8), trace_lids=np.zeros((ne.value, nu), np.int32),
+               trace_side=np.zeros(nt.value, np.uint8), ndof=nd.value, ntrace=nt.value, nelem=ne.value, dim=dim)
+    _check(lib.mha_mesh_porous_hybrid(dim, vp(nc), vp(lo), vp(hi), vp(out["nodes"]), vp(out["lids"]), vp(out["offsets"]),
+                                      vp(out["orient"]), vp(out["trace_lids"]), vp(out["trace_side"])))
+    return out
+
+
+def check_dg_lids(lids, nrows):
+    """Host-only test hook (csrc/test_hooks.h): the DG check of the porousMixedHybridized element step; raises MhaError."""
+    lids = _np(lids, np.int32)
+    f = load_library().mha_test_pmh_check_dg
+    f.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+    _check(f(lids.shape[0], lids.shape[1], int(nrows), lids.ctypes.data_as(C.c_void_p)))
+
+
+def module_parameter(physics, dim, name, value=1.0, as_vector=False):
+    """Host-only test hook (csrc/test_hooks.h): what a fresh module of `physics` says to a setting; raises MhaError."""
+    f = load_library().mha_test_module_parameter
+    f.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_double, C.c_int]
+    _check(f(MODULE_IDS[physics], int(dim), name.encode(), float(value), int(as_vector)))
+
+
 def check_swhdg_subgrids(m, nodes, lids, offsets, nrows):
     """Host-only test hook (csrc/test_hooks.h, not part of the boundary): the layout check of Block.set_swhdg_subgrids
     on host arrays; raises MhaError."""
@@ -757,9 +809,9 @@ class Block:
         self.dim, self.order = dim, order
         self._keep = []
         if physics is not None:
-            if physics not in ALL_PHYSICS_IDS:
+            if physics not in MODULE_IDS:
                 raise ValueError(physics)
-            _check(lib.mha_physics_select(self._h, ALL_PHYSICS_IDS[physics]))
+            _check(lib.mha_physics_select(self._h, MODULE_IDS[physics]))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -917,6 +969,17 @@ class Block:
         _check(lib.mha_swhdg_condensed_element(self._h, _ptr(u), _ptr(u_prev), _ptr(u_stage), _ptr(lam), _ptr(side_types),
                                                None if ff is None else ff.ctypes.data_as(C.c_void_p), _ptr(schur), _ptr(gvec),
                                                _ptr(du), _ptr(num_singular)))
+
+    def pmh_element_blocks(self, u, lam, res=None, blocks=None):
+        """The uncondensed element block of porousMixedHybridized by the plain kernel (mha_pmh_element_blocks): fills the CUDA
+        tensors res [E][n] = -res.val(), blocks [E][n][n] (n = 1 + 4 dim: p, u, then the traces in HFACE order)."""
+        _check(load_library().mha_pmh_element_blocks(self._h, _ptr(u), _ptr(lam), _ptr(res), _ptr(blocks)))
+
+    def pmh_condensed_element(self, u, lam, schur=None, gvec=None, du=None, num_singular=None):
+        """The element step of porousMixedHybridized in one kernel (mha_pmh_condensed_element): fills the given CUDA tensors
+        schur [E][2dim][2dim], gvec [E][2dim], du [E][1+2dim]; num_singular: int32 device counter, incremented.  No sync."""
+        _check(load_library().mha_pmh_condensed_element(self._h, _ptr(u), _ptr(lam), _ptr(schur), _ptr(gvec), _ptr(du),
+                                                        _ptr(num_singular)))
 
     def set_swhdg_subgrids(self, m):
         """Declare elements [k m^2, (k+1) m^2) as macro element k's m x m sub-mesh (mha_swhdg_set_subgrids; validated on the

@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "porous_data.hpp"
+#include "porous_hybrid.hpp"
 #include "porous_plan.hpp"
 #include "row_owner_plan.hpp"
 
@@ -129,6 +130,7 @@ void AssemblyManager::setMesh(int nelem, const double *nodes, const int32_t *lid
   else d_fixed_.resize(0);
   has_mesh_ = true;
   subgrid_checked_ = false;
+  pmh_dg_checked_ = false;
   subgrid_m_ = 0;
   has_graph_ = false;
   porous_direct_ = -1;
@@ -956,7 +958,7 @@ void AssemblyManager::getMass(const double *masswts, double *local_mass) {
   VarLayoutDev vl = layout_;
   vl.orient = has_orient_ ? d_orient_.data() : nullptr;
   PhysParamsDev pp;
-  pp.physics = -physics_->id;  // negative id = mass mode on the module's variable layout
+  pp.physics = -physics_->pointModuleId();  // negative id = mass mode on the module's variable layout
   for (size_t v = 0; v < vars_.size(); ++v) pp.p[v] = masswts ? masswts[v] : 1.0;
   ElemOut o;
   o.compute_jacobian = 1;
@@ -1023,6 +1025,52 @@ void AssemblyManager::swhdgCondensedElement(const double *u, const double *u_pre
   const SwhStep s = swhStepArgs(u, u_prev, u_stage, lambda, side_types, farfield, false);
   timedBegin();
   launch_swhdg_fused(blockDev(), sideTablesDev(), s.a, time_, s.pp, o, stream_);
+  timedEnd();
+}
+
+// What the two element steps of porousMixedHybridized share.  The module has no time-derivative term and its element step
+// is stated for a steady Newton residual: a transient context is refused.  The DG check runs on the host copy of the
+// LIDs, once per mesh, before anything is launched.
+PmhElementDev AssemblyManager::pmhStepArgs(const double *u, const double *lambda) {
+  requireReady(false);
+  porousMixedHybridized *pm = dynamic_cast<porousMixedHybridized *>(physics_.get());
+  MHA_REQUIRE(pm != nullptr, MHA_ERR_INVALID, "the block's physics module is not porousMixedHybridized");
+  MHA_REQUIRE(lambda != nullptr, MHA_ERR_INVALID, "null trace values");
+  MHA_REQUIRE(!time_.transient, MHA_ERR_INVALID,
+              "porousMixedHybridized: the element step is a steady residual (the module has no time-derivative term); the "
+              "context is transient");
+  if (!pmh_dg_checked_) {
+    check_dg_lids(nelem_, n_, nrows_, h_lids_.data());
+    pmh_dg_checked_ = true;
+  }
+  bindState(u, nullptr, nullptr);
+  prepareSideTables();
+  PmhElementDev a = pm->elementArgs(dim_);
+  a.lambda = lambda;
+  a.orient = has_orient_ ? d_orient_.data() : nullptr;
+  return a;
+}
+
+void AssemblyManager::pmhElementBlocks(const double *u, const double *lambda, double *res, double *blocks) {
+  MHA_REQUIRE(res || blocks, MHA_ERR_INVALID, "no output requested");
+  PmhElementDev a = pmhStepArgs(u, lambda);
+  a.res = res;
+  a.blocks = blocks;
+  timedBegin();
+  launch_porous_hybrid_blocks(blockDev(), sideTablesDev(), a, time_, stream_);
+  timedEnd();
+}
+
+void AssemblyManager::pmhCondensedElement(const double *u, const double *lambda, double *schur, double *gvec, double *du,
+                                          int32_t *num_singular) {
+  MHA_REQUIRE(schur || gvec || du, MHA_ERR_INVALID, "no output requested");
+  PmhElementDev a = pmhStepArgs(u, lambda);
+  a.schur = schur;
+  a.gvec = gvec;
+  a.du = du;
+  a.singular = num_singular;
+  timedBegin();
+  launch_porous_hybrid_fused(blockDev(), sideTablesDev(), a, time_, stream_);
   timedEnd();
 }
 

@@ -80,6 +80,10 @@ class AssemblyManager {
                              const uint8_t *side_types, const double *farfield, SwhFusedOut out);
   void swhdgSubgridBlocks(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
                           const uint8_t *side_types, const double *farfield, double *res, double *blocks);
+  // the element step of porousMixedHybridized (kernels/porous_hybrid_blocks.hip, kernels/porous_hybrid_fused.hip): the
+  // uncondensed block by the plain kernel; geometry, local matrices, interior solve and Schur complement in one launch
+  void pmhElementBlocks(const double *u, const double *lambda, double *res, double *blocks);
+  void pmhCondensedElement(const double *u, const double *lambda, double *schur, double *gvec, double *du, int32_t *num_singular);
   void scatterLocal(const double *local_J, const double *local_res, double *res, double *crs_vals);
   // boundary groups (reference: src/tools/boundaryGroup.hpp, assemblyManager.cpp:2518-2638)
   int addBoundaryGroup(const std::string &sidename, int bc_type, int num, const int32_t *elem_ids,
@@ -147,6 +151,10 @@ class AssemblyManager {
   struct SwhStep { SwhElementDev a; PhysParamsDev pp; };
   SwhStep swhStepArgs(const double *u, const double *u_prev, const double *u_stage, const double *lambda,
                       const uint8_t *side_types, const double *farfield, bool need_layout);
+  // shared setup of the two porousMixedHybridized element steps: module, steady state, DG LIDs (once per mesh), side
+  // tables, the kernels' arguments without their outputs
+  PmhElementDev pmhStepArgs(const double *u, const double *lambda);
+  bool pmh_dg_checked_ = false;
   void timedBegin();
   void timedEnd();
 

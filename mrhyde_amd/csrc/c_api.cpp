@@ -14,6 +14,7 @@
 #include "newton.hpp"
 #include "porous_data.hpp"
 #include "porous_plan.hpp"
+#include "porous_hybrid.hpp"
 #include "row_owner_plan.hpp"
 #include "test_hooks.h"
 #include "scatter_plan.hpp"
@@ -545,6 +546,44 @@ int mha_swhdg_condensed_element(mha_context *ctx, const double *u, const double 
     o.du = du;
     o.singular = num_singular;
     mgr(ctx).swhdgCondensedElement(u, u_prev, u_stage, lambda, side_types, farfield_host, o);
+  });
+}
+
+int mha_pmh_element_blocks(mha_context *ctx, const double *u, const double *lambda, double *res, double *blocks) {
+  return guarded([&] { mgr(ctx).pmhElementBlocks(u, lambda, res, blocks); });
+}
+
+int mha_pmh_condensed_element(mha_context *ctx, const double *u, const double *lambda, double *schur, double *gvec,
+                              double *du, int32_t *num_singular) {
+  return guarded([&] { mgr(ctx).pmhCondensedElement(u, lambda, schur, gvec, du, num_singular); });
+}
+
+int mha_mesh_porous_hybrid_sizes(int dim, const int *ncell, int *nelem, int64_t *ndof, int64_t *ntrace) {
+  return guarded([&] {
+    MHA_REQUIRE(ncell && nelem && ndof && ntrace, MHA_ERR_INVALID, "null argument");
+    mha::mesh_porous_hybrid_sizes(dim, ncell, nelem, ndof, ntrace);
+  });
+}
+
+int mha_mesh_porous_hybrid(int dim, const int *ncell, const double *lo, const double *hi, double *nodes, int32_t *lids,
+                           int32_t *offsets, int8_t *orient, int32_t *trace_lids, uint8_t *trace_side) {
+  return guarded([&] {
+    MHA_REQUIRE(ncell && lo && hi && nodes && lids && offsets && orient && trace_lids && trace_side, MHA_ERR_INVALID,
+                "null argument");
+    mha::mesh_porous_hybrid(dim, ncell, lo, hi, nodes, lids, offsets, orient, trace_lids, trace_side);
+  });
+}
+
+int mha_test_pmh_check_dg(int num_elems, int n, int num_rows, const int32_t *lids) {
+  return guarded([&] { mha::check_dg_lids(num_elems, n, num_rows, lids); });
+}
+
+int mha_test_module_parameter(int physics_id, int dim, const char *name, double value, int as_vector) {
+  return guarded([&] {
+    MHA_REQUIRE(name, MHA_ERR_INVALID, "null argument");
+    const std::unique_ptr<mha::PhysicsBase> module = mha::import_physics(physics_id, dim);
+    if (as_vector) module->setParameterVector(name, &value, 1);
+    else module->setParameter(name, value);
   });
 }
 

@@ -361,6 +361,23 @@ struct SwhFusedOut {
   int32_t *iters = nullptr, *active = nullptr;
 };
 
+// The element step of porousMixedHybridized (kernels/porous_hybrid_blocks.hip, kernels/porous_hybrid_fused.hip).
+// Unknowns of an element: p, the 2 dim flux dofs (dof 2 c + s: direction c, low / high side), then the 2 dim traces in
+// HFACE order (left, bottom, right, top[, front, back]); n_int = 1 + 2 dim, n = n_int + 2 dim.
+struct PmhElementDev {
+  const double *lambda = nullptr;  // [E][2 dim] trace unknowns, HFACE face order
+  const int8_t *orient = nullptr;  // [E][n_int] basis signs in (variable, dof) order, or null
+  FuncDesc f[4];                   // source, Kinv_xx, Kinv_yy, Kinv_zz at the volume points
+  const double *edata = nullptr;   // [E][ecols]: Kinv_dd = 1 / column 0 ("use permeability data"); null: the functions
+  int ecols = 0;
+  double *res = nullptr;           // plain kernel: [E][n] -res.val()
+  double *blocks = nullptr;        //               [E][n][n] res(r).dx(c), stored
+  double *schur = nullptr;         // fused kernel: [E][2 dim][2 dim], [E][2 dim], [E][n_int] as condense.hip defines them
+  double *gvec = nullptr;
+  double *du = nullptr;
+  int *singular = nullptr;         //               += 1 per element with a non-positive pivot
+};
+
 // Row blocks keyed by assembly pattern (block_pattern.hpp) for the matrix-core row-owner Jacobian.
 struct BlockPatternDev {
   int num_wgs = 0, max_w_doubles = 0;

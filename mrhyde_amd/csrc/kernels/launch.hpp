@@ -197,6 +197,13 @@ void launch_swhdg_subgrid_fused(int m, const BlockDev &b, const SideTablesDev &s
                                 const PhysParamsDev &pp, const SwhFusedOut &o, hipStream_t stream);
 void launch_swhdg_subgrid_blocks(int m, const BlockDev &b, const SideTablesDev &st, const SwhElementDev &a, const TimeDev &tm,
                                  const PhysParamsDev &pp, hipStream_t stream);
+// porous_hybrid_blocks.hip: the uncondensed element block of porousMixedHybridized (a.res, a.blocks), plain and unfused;
+// porous_hybrid_fused.hip: the same step with the interior solve and the Schur complement inside, one thread per element
+// (a.schur, a.gvec, a.du, 16-byte aligned; a.singular)
+void launch_porous_hybrid_blocks(const BlockDev &b, const SideTablesDev &st, const PmhElementDev &a, const TimeDev &tm,
+                                 hipStream_t stream);
+void launch_porous_hybrid_fused(const BlockDev &b, const SideTablesDev &st, const PmhElementDev &a, const TimeDev &tm,
+                                hipStream_t stream);
 void launch_condense(int n_int, int n_trace, int64_t nelem, const double *blocks, const double *res, double *schur,
                      double *gvec, double *du, int *singular, hipStream_t stream);
 

@@ -375,6 +375,60 @@ void mesh_swhdg_subgrids(const int *nc, int m, const double *lo, const double *h
     }
 }
 
+void mesh_porous_hybrid_sizes(int dim, const int *nc, int *nelem, int64_t *ndof, int64_t *ntrace) {
+  MHA_REQUIRE(dim == 2 || dim == 3, MHA_ERR_INVALID, "porous hybrid mesh: dimension must be 2 or 3 (quads, hexes)");
+  int64_t ne = 1, nt = 0;
+  for (int d = 0; d < dim; ++d) {
+    MHA_REQUIRE(nc[d] > 0, MHA_ERR_INVALID, "porous hybrid mesh: ncell must be positive");
+    ne *= nc[d];
+  }
+  for (int c = 0; c < dim; ++c) {
+    int64_t m = 1;
+    for (int d = 0; d < dim; ++d) m *= nc[d] + (d == c);
+    nt += m;
+  }
+  MHA_REQUIRE(ne * (1 + 2 * dim) < (int64_t{1} << 31), MHA_ERR_INVALID, "porous hybrid mesh: too many elements for 32-bit LIDs");
+  *nelem = static_cast<int>(ne);
+  *ndof = ne * (1 + 2 * dim);
+  *ntrace = nt;
+}
+
+void mesh_porous_hybrid(int dim, const int *nc, const double *lo, const double *hi, double *nodes, int32_t *lids,
+                        int32_t *offsets, int8_t *orient, int32_t *trace_lids, uint8_t *trace_side) {
+  int nelem;
+  int64_t ndof, ntrace;
+  mesh_porous_hybrid_sizes(dim, nc, &nelem, &ndof, &ntrace);
+  // the conforming p (HVOL) / u (HDIV) mesh: vertices, face numbering, face signs and boundary marks come from it
+  const int types[2] = {MHA_BASIS_HVOL, MHA_BASIS_HDIV}, orders[2] = {0, 1};
+  int nverts, ne, n_tot;
+  int64_t nconf;
+  mesh_multi_sizes(dim, nc, 2, types, orders, &nverts, &ne, &n_tot, &nconf);
+  const int nn = 1 << dim, nu = 2 * dim, ni = 1 + nu;
+  MHA_REQUIRE(ne == nelem && n_tot == ni, MHA_ERR_STATE, "porous hybrid mesh: size mismatch with the conforming mesh");
+  std::vector<double> verts(static_cast<size_t>(nverts) * dim);
+  std::vector<int32_t> c2v(static_cast<size_t>(nelem) * nn), clids(static_cast<size_t>(nelem) * ni), coffs(ni), dof_var(nconf);
+  std::vector<uint8_t> mask(nconf);
+  mesh_structured_multi(dim, nc, lo, hi, 2, types, orders, verts.data(), c2v.data(), clids.data(), coffs.data(), orient,
+                        mask.data(), dof_var.data());
+  const int64_t face_base = nconf - ntrace;  // the face dofs are the last of the conforming map
+  for (int k = 0; k < ni; ++k) offsets[k] = k;
+  for (int e = 0; e < nelem; ++e) {
+    for (int v = 0; v < nn; ++v)
+      for (int d = 0; d < dim; ++d)
+        nodes[(static_cast<size_t>(e) * nn + v) * dim + d] = verts[static_cast<size_t>(c2v[static_cast<size_t>(e) * nn + v]) * dim + d];
+    for (int k = 0; k < ni; ++k) lids[static_cast<size_t>(e) * ni + k] = e * ni + k;
+    for (int k = 0; k < nu; ++k) {
+      const int f = k < 4 ? 2 * (k & 1) + (k >> 1) : k;  // HFACE face k -> flux dof 2 c + s
+      const int32_t row = clids[static_cast<size_t>(e) * ni + coffs[1 + f]];
+      MHA_REQUIRE(row >= face_base && row < nconf, MHA_ERR_STATE, "porous hybrid mesh: face dof outside the face range");
+      trace_lids[static_cast<size_t>(e) * nu + k] = static_cast<int32_t>(row - face_base);
+      const int c = f >> 1;
+      const uint8_t m = mask[row];
+      trace_side[row - face_base] = (m & (1u << (2 * c))) ? 1 + 2 * c : (m & (1u << (2 * c + 1))) ? 2 + 2 * c : 0;
+    }
+  }
+}
+
 void check_swhdg_subgrids(int m, int nelem, int nrows, const double *nodes, const int32_t *lids, const int32_t *offs) {
   MHA_REQUIRE(m >= 1 && m <= 4, MHA_ERR_INVALID,
               "HDG subgrids: m = " << m << " sub-elements per direction is outside 1..4 (the dense interior solve holds n_int = 3 (m+1)^2 <= 75 unknowns in LDS)");

@@ -32,6 +32,15 @@ void mesh_swhdg_subgrids_sizes(const int *ncell_macro, int m, int *nelem, int64_
 void mesh_swhdg_subgrids(const int *ncell_macro, int m, const double *lo, const double *hi, double *nodes, int32_t *lids,
                          int32_t *offsets, int32_t *trace_lids);
 
+// Mesh of a porousMixedHybridized block (mha_mesh_porous_hybrid): nc[dim] cells on [lo, hi], dim = 2 or 3.  DG unknowns
+// p, u of every element (lids[e][k] = e (1 + 2 dim) + k, offsets the identity), the face signs mesh_structured_multi gives
+// conforming HDIV, one trace row per face of the mesh (faces numbered direction by direction, as the HDIV dofs of
+// mesh_structured_multi) listed per element in HFACE order (left, bottom, right, top[, front, back]), and per trace row
+// 0 (interior) or 1 + side (0 left, 1 right, 2 bottom, 3 top, 4 front, 5 back).
+void mesh_porous_hybrid_sizes(int dim, const int *nc, int *nelem, int64_t *ndof, int64_t *ntrace);
+void mesh_porous_hybrid(int dim, const int *nc, const double *lo, const double *hi, double *nodes, int32_t *lids,
+                        int32_t *offsets, int8_t *orient, int32_t *trace_lids, uint8_t *trace_side);
+
 // The layout check of mha_swhdg_set_subgrids (throws MHA_ERR_INVALID): elements [k m^2, (k+1) m^2) are macro element k's
 // m x m sub-mesh, row-major with x fastest; its rows are shared only inside k with the Q1 connectivity of an m x m grid;
 // its vertices are the bilinear image of the uniform subdivision of the macro quad to 1e-12 x its size.  m in 1..4.

@@ -113,6 +113,9 @@ class PhysicsBase {
   virtual bool heterogeneous() const { return false; }
 
   int id = 0;  // MHA_PHYSICS_*, set by import_physics
+  // the module whose point function and variable layout the volume term runs on (engine_dispatch.hpp): its own, unless
+  // the volume form is another module's (porousMixedHybridized: porousMixed's)
+  virtual int pointModuleId() const { return id; }
   std::string label;
   Workset *wkset = nullptr;
   FunctionManager *functionManager = nullptr;
@@ -165,8 +168,10 @@ class porousMixed : public PhysicsBase {
   // the term added twice to KL_xx, once to KL_yy, never to KL_zz
   bool fix_KL_3d = false;
 
+ protected:
+  PorousHetDev hetParams();  // (also the element data of porousMixedHybridized, porous_hybrid.hpp)
+
  private:
-  PorousHetDev hetParams();
   void buildKLTables(int dim);
   int klN_[3] = {-1, -1, -1};
   double klL_[3] = {0, 0, 0}, klSigma_[3] = {0, 0, 0}, klEta_[3] = {0, 0, 0};

@@ -109,6 +109,14 @@ int mha_test_module_rules(int physics_id, int dim, int num_vars, const int32_t *
                           const int32_t *cards, int bc_type, const char *sidename, int n, int block_order, int nqs,
                           int define_neumann_e);
 
+/* What a physics module says to a scalar setting (as_vector == 0: PhysicsBase::setParameter) or to a parameter vector of
+ * one entry (as_vector != 0: setParameterVector), asked of a fresh module of import_physics; no block, no device. */
+int mha_test_module_parameter(int physics_id, int dim, const char *name, double value, int as_vector);
+
+/* The DG check of the porousMixedHybridized element step alone (porous_hybrid.hpp, check_dg_lids) on a host LID map
+ * lids [num_elems][n]: every LID in [0, num_rows) and in exactly one element.  Stateless. */
+int mha_test_pmh_check_dg(int num_elems, int n, int num_rows, const int32_t *lids);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@
 #include "linearelasticity.hpp"
 #include "cdr.hpp"
 #include "helmholtz.hpp"
+#include "porous_hybrid.hpp"
 
 #include "expression.hpp"
 #include "porous_data.hpp"
@@ -592,6 +593,7 @@ std::unique_ptr<PhysicsBase> import_physics(int physics_id, int dim) {
   if (physics_id == MHA_PHYSICS_POROUS_MIXED) p.reset(new porousMixed());
   if (physics_id == MHA_PHYSICS_NAVIERSTOKES) p.reset(new navierstokes(dim));
   if (physics_id == MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED) p.reset(new shallowwaterHybridized());
+  if (physics_id == MHA_PHYSICS_POROUS_MIXED_HYBRIDIZED) p.reset(new porousMixedHybridized());
   MHA_REQUIRE(p != nullptr, MHA_ERR_INVALID, "unknown physics module id " << physics_id);
   p->id = physics_id;
   return p;
