@@ -220,6 +220,24 @@ int mha_get_graph(mha_context *ctx, int32_t *rowptr_host, int32_t *colind_host);
  * or HFACE above lowest order, triangles and tetrahedra, the multiscale interface / "aux p" coupling.                  */
 /* (id 12: + 4 stays unassigned, the module-rule tests pin 11 as an id that names no module) */
 #define MHA_PHYSICS_POROUS_MIXED_HYBRIDIZED (MHA_PHYSICS_LINEARELASTICITY_THERMAL + 5)
+/* porousWeakGalerkin, weak Galerkin Darcy flow (src/physics/porousWeakGalerkin.cpp; the deck's module name is "porous
+ * weak Galerkin"): pint (HVOL 0), pbndry (HFACE 0), the weak gradient u (HDIV-DG 1) and the flux t (HDIV-DG 1) of :14-64.
+ * The BLOCK holds pint, u and t, in that order, on 2-D quads and 3-D hexes, with DG LIDs (checked on the host by the
+ * element step, once per mesh); pbndry, one constant per face, is no block variable: it arrives as data per element,
+ * lambda[E][2 dim], and its rows live in the caller's trace system.  Functions (:69-88): "source" (0) and "perm" (1):
+ * constants, arrays, closed forms or deck strings in the coordinates.  Parameter "use permeability data" (:58, updatePerm
+ * :601-609): perm = data(elem, 0) of the block's element data -- the value itself, not its inverse as in porousMixed; it
+ * may stand beside a deck-string source.  volumeResidual (:94-323) runs on the point function porous_wg_point:
+ * mha_assemble_jacres, mha_compute_local_jacres, mha_apply_jacobian, mha_apply_jacobian_multi, mha_jacobian_diagonal,
+ * mha_get_mass and the workset views (pint, u[x], div(u), t[y], div(t)) work on the block.  faceResidual (:424-505) on all
+ * 2 dim faces of every element is the element step mha_pwg_element_blocks / mha_pwg_condensed_element below.  Dirichlet
+ * data enters as the decks give it, `Dirichlet conditions: pbndry`: fixed trace rows and the values in lambda.  Refused
+ * with MHA_ERR_INVALID: "useAC" other than 0 (HDIV_AC is not built), any order above lowest, KL options and parameter
+ * vectors, deck strings that read the solution fields, boundary groups of the module (the weak "Dirichlet pbndry" and
+ * "interface" branches of boundaryResidual :329-417), mha_compute_flux (:511-554), 1-D, MHA_ASSEMBLE_DETERMINISTIC,
+ * MHA_PATH_ROW_OWNER, a transient state in the element step.  Not built: triangles and tetrahedra, the multiscale
+ * interface / "aux pbndry" coupling.  (id 13; 11 stays unassigned, see above) */
+#define MHA_PHYSICS_POROUS_WEAK_GALERKIN (MHA_PHYSICS_LINEARELASTICITY_THERMAL + 6)
 int mha_physics_select(mha_context *ctx, int physics_id);
 #define MHA_FUNC_CONSTANT 0
 #define MHA_FUNC_IP_ARRAY 1     /* dev pointer to [E][numip] f64                    */
@@ -811,6 +829,39 @@ int mha_pmh_condensed_element(mha_context *ctx, const double *u_dev, const doubl
 int mha_mesh_porous_hybrid_sizes(int dim, const int *ncell, int *nelem, int64_t *ndof, int64_t *ntrace);
 int mha_mesh_porous_hybrid(int dim, const int *ncell, const double *lo, const double *hi, double *nodes, int32_t *lids,
                            int32_t *offsets, int8_t *orient, int32_t *trace_lids, uint8_t *trace_side);
+/* ---- porousWeakGalerkin: the element step ---------------------------------------------------------------------------
+ * replaces: porousWeakGalerkin::volumeResidual + faceResidual (src/physics/porousWeakGalerkin.cpp:94-323, 424-505) on
+ * every element and all of its 2 dim faces, in the layout and conventions of the porousMixedHybridized entry points
+ * above.  Unknowns of an element: pint, the 2 dim dofs of u, the 2 dim dofs of t (dof 2 c + s as above), then the 2 dim
+ * traces pbndry in HFACE order; n_int = 1 + 4 dim, n = 1 + 6 dim (13 or 19).
+ *   R_pint = int (div t - source) q,              R_u = int u . v + pint div v - sum_faces int_F pbndry (v . n),
+ *   R_t = int (perm u + t) . s,                   R_pbndry = - sum_faces int_F (t . n) mu.
+ * u_dev[nrows] is the block's state (steady; a transient context is refused), lambda_dev[E][2 dim] the traces.
+ * mha_pwg_element_blocks: res_dev[E][n] = -res.val(), blocks_dev[E][n][n] = d res / d unknown (either may be NULL), by a
+ * plain kernel, one thread per (element, row), every volume and side point of general quads and hexes: the
+ * implementation the fused kernel is compared with, through mha_batched_condense.  The structurally empty sub-blocks
+ * (pint-pint, pint-u, pint-lambda, u-t, t-pint, t-lambda, lambda-pint, lambda-u, lambda-lambda) are exactly +0.0.
+ * mha_pwg_condensed_element: the same step with the interior solve and the Schur complement inside, one launch, one
+ * thread per element; schur_dev[E][2 dim][2 dim], gvec_dev[E][2 dim], du_dev[E][n_int] as mha_batched_condense defines
+ * them (any may be NULL, not all; each 16-byte aligned) are all that is written, in whole 16-byte pieces that are
+ * contiguous across a wavefront.  No pivot search: with M = (v_f, v_g) = L L^T, K = (perm v_f, v_g), B = (1, div v_f),
+ * C_k = <v_f(k) . n, 1>:  W = M^-1 K M^-1,  Z = W B,  sigma = B^T W B > 0,
+ *   dp = (r_p - B^T M^-1 r_t + Z^T r_u) / sigma,  du = M^-1 (r_u - B dp),  dt = M^-1 (r_t - K du),
+ *   S_ab = C_a C_b (W_ab - Z_a Z_b / sigma),      g_a = r_lambda,a + C_a dt_a.
+ * A non-positive Cholesky pivot or sigma <= 0 (degenerate element, perm <= 0) is counted into *num_singular_dev (device
+ * counter, may be NULL); that element's outputs are unspecified but finite.  Enqueued on the context's stream: no host
+ * synchronisation, no allocation after the first call on a mesh.  No floating-point atomics: two runs are bit-identical.
+ * The linear solve on one block is the two calls of porousMixedHybridized.                                            */
+int mha_pwg_element_blocks(mha_context *ctx, const double *u_dev, const double *lambda_dev, double *res_dev,
+                           double *blocks_dev);
+int mha_pwg_condensed_element(mha_context *ctx, const double *u_dev, const double *lambda_dev, double *schur_dev,
+                              double *gvec_dev, double *du_dev, int32_t *num_singular_dev);
+/* Mesh helper (input generation, host only) for a porousWeakGalerkin block: nodes, trace_lids, trace_side and ntrace as
+ * mha_mesh_porous_hybrid gives them; lids[E][1 + 4 dim] (every LID once), offsets[1 + 4 dim] and orient[E][1 + 4 dim]
+ * (u and t carry the same face signs); ndof = nelem (1 + 4 dim).                                                       */
+int mha_mesh_porous_weak_galerkin_sizes(int dim, const int *ncell, int *nelem, int64_t *ndof, int64_t *ntrace);
+int mha_mesh_porous_weak_galerkin(int dim, const int *ncell, const double *lo, const double *hi, double *nodes,
+                                  int32_t *lids, int32_t *offsets, int8_t *orient, int32_t *trace_lids, uint8_t *trace_side);
 /* Batched static condensation of element blocks: eliminates the n_int interior unknowns of every element.
  * replaces: the element-local direct solve of the subgrid solver and its forward sensitivities d u / d lambda
  * (SubGridDtN_Solver, src/subgrid/subgridDtN_solver.cpp:681-903, 1542-1616) in Schur-complement form.

@@ -36,6 +36,8 @@ EXPORTS = [
     "mha_jacobian_diagonal", "mha_apply_jacobian_multi", "mha_apply_boundary_jacobian",
     "mha_boundary_jacobian_diagonal",
     "mha_pmh_element_blocks", "mha_pmh_condensed_element", "mha_mesh_porous_hybrid_sizes", "mha_mesh_porous_hybrid",
+    "mha_pwg_element_blocks", "mha_pwg_condensed_element", "mha_mesh_porous_weak_galerkin_sizes",
+    "mha_mesh_porous_weak_galerkin",
 ]
 KL_MAX_TERMS = 8  # MHA_KL_MAX_TERMS: KL roots per direction the kernels evaluate
 MASS_ON_THE_FLY, MASS_LOCAL, MASS_DATABASE, MASS_DATABASE_SPARSE = 0, 1, 2, 3
@@ -64,7 +66,10 @@ ALL_PHYSICS_IDS = dict(PHYSICS_IDS, helmholtz=PHYSICS_HELMHOLTZ)
 # unassigned (tests/test_module_rules.py pins it as an id that names no module, and ALL_PHYSICS_IDS as the table of the
 # ten modules before this one); Block looks a name up in MODULE_IDS, which holds every module.
 PHYSICS_POROUS_MIXED_HYBRIDIZED = 12
-MODULE_IDS = dict(ALL_PHYSICS_IDS, porousMixedHybridized=PHYSICS_POROUS_MIXED_HYBRIDIZED)
+# porousWeakGalerkin: pint (HVOL), u, t (HDIV-DG) on the block, the trace pbndry (HFACE) as data per element
+PHYSICS_POROUS_WEAK_GALERKIN = 13
+MODULE_IDS = dict(ALL_PHYSICS_IDS, porousMixedHybridized=PHYSICS_POROUS_MIXED_HYBRIDIZED,
+                  porousWeakGalerkin=PHYSICS_POROUS_WEAK_GALERKIN)
 PATH_POINT_ENGINE = 4
 PATH_ROW_GATHER = 5
 BC_NEUMANN, BC_WEAK_DIRICHLET, BC_FLUX = 1, 2, 3
@@ -180,6 +185,10 @@ def load_library():
         _lib.mha_pmh_condensed_element.argtypes = [C.c_void_p] * 7
         _lib.mha_mesh_porous_hybrid_sizes.argtypes = [C.c_int] + [C.c_void_p] * 4
         _lib.mha_mesh_porous_hybrid.argtypes = [C.c_int] + [C.c_void_p] * 9
+        _lib.mha_pwg_element_blocks.argtypes = [C.c_void_p] * 5
+        _lib.mha_pwg_condensed_element.argtypes = [C.c_void_p] * 7
+        _lib.mha_mesh_porous_weak_galerkin_sizes.argtypes = [C.c_int] + [C.c_void_p] * 4
+        _lib.mha_mesh_porous_weak_galerkin.argtypes = [C.c_int] + [C.c_void_p] * 9
     return _lib
 
 
@@ -532,6 +541,29 @@ def mesh_porous_hybrid(ncell, lo=None, hi=None):
                trace_side=np.zeros(nt.value, np.uint8), ndof=nd.value, ntrace=nt.value, nelem=ne.value, dim=dim)
     _check(lib.mha_mesh_porous_hybrid(dim, vp(nc), vp(lo), vp(hi), vp(out["nodes"]), vp(out["lids"]), vp(out["offsets"]),
                                       vp(out["orient"]), vp(out["trace_lids"]), vp(out["trace_side"])))
+    return out
+
+
+def mesh_porous_weak_galerkin(ncell, lo=None, hi=None):
+    """Mesh of a porousWeakGalerkin block (mha_mesh_porous_weak_galerkin): len(ncell) = 2 (quads) or 3 (hexes).
+    -> dict as mesh_porous_hybrid gives it, with the same nodes, trace_lids, trace_side and ntrace; lids [E][1+4dim] (DG:
+    pint, u, t), offsets, orient [E][1+4dim] (u and t carry the same face signs), ndof = nelem (1 + 4 dim)."""
+    lib = load_library()
+    nc = _np(ncell, np.int32)
+    dim = len(nc)
+    lo = _np(np.zeros(dim) if lo is None else lo, np.float64)
+    hi = _np(np.ones(dim) if hi is None else hi, np.float64)
+    if dim not in (2, 3) or len(lo) != dim or len(hi) != dim:
+        raise ValueError("mesh_porous_weak_galerkin: ncell, lo, hi of length 2 or 3")
+    ne, nd, nt = C.c_int(), C.c_int64(), C.c_int64()
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    _check(lib.mha_mesh_porous_weak_galerkin_sizes(dim, vp(nc), C.byref(ne), C.byref(nd), C.byref(nt)))
+    ni, nu = 1 + 4 * dim, 2 * dim
+    out = dict(nodes=np.zeros((ne.value, 2 ** dim, dim)), lids=np.zeros((ne.value, ni), np.int32), offsets=np.zeros(ni, np.int32),
+               orient=np.ones((ne.value, ni), np.int8), trace_lids=np.zeros((ne.value, nu), np.int32),
+               trace_side=np.zeros(nt.value, np.uint8), ndof=nd.value, ntrace=nt.value, nelem=ne.value, dim=dim)
+    _check(lib.mha_mesh_porous_weak_galerkin(dim, vp(nc), vp(lo), vp(hi), vp(out["nodes"]), vp(out["lids"]), vp(out["offsets"]),
+                                             vp(out["orient"]), vp(out["trace_lids"]), vp(out["trace_side"])))
     return out
 
 
@@ -979,6 +1011,17 @@ class Block:
         """The element step of porousMixedHybridized in one kernel (mha_pmh_condensed_element): fills the given CUDA tensors
         schur [E][2dim][2dim], gvec [E][2dim], du [E][1+2dim]; num_singular: int32 device counter, incremented.  No sync."""
         _check(load_library().mha_pmh_condensed_element(self._h, _ptr(u), _ptr(lam), _ptr(schur), _ptr(gvec), _ptr(du),
+                                                        _ptr(num_singular)))
+
+    def pwg_element_blocks(self, u, lam, res=None, blocks=None):
+        """The uncondensed element block of porousWeakGalerkin by the plain kernel (mha_pwg_element_blocks): fills the CUDA
+        tensors res [E][n] = -res.val(), blocks [E][n][n] (n = 1 + 6 dim: pint, u, t, then the traces in HFACE order)."""
+        _check(load_library().mha_pwg_element_blocks(self._h, _ptr(u), _ptr(lam), _ptr(res), _ptr(blocks)))
+
+    def pwg_condensed_element(self, u, lam, schur=None, gvec=None, du=None, num_singular=None):
+        """The element step of porousWeakGalerkin in one kernel (mha_pwg_condensed_element): fills the given CUDA tensors
+        schur [E][2dim][2dim], gvec [E][2dim], du [E][1+4dim]; num_singular: int32 device counter, incremented.  No sync."""
+        _check(load_library().mha_pwg_condensed_element(self._h, _ptr(u), _ptr(lam), _ptr(schur), _ptr(gvec), _ptr(du),
                                                         _ptr(num_singular)))
 
     def set_swhdg_subgrids(self, m):

@@ -10,6 +10,7 @@
 
 #include "porous_data.hpp"
 #include "porous_hybrid.hpp"
+#include "porous_weak_galerkin.hpp"
 #include "porous_plan.hpp"
 #include "row_owner_plan.hpp"
 
@@ -1071,6 +1072,50 @@ void AssemblyManager::pmhCondensedElement(const double *u, const double *lambda,
   a.singular = num_singular;
   timedBegin();
   launch_porous_hybrid_fused(blockDev(), sideTablesDev(), a, time_, stream_);
+  timedEnd();
+}
+
+// What the two element steps of porousWeakGalerkin share: as pmhStepArgs, with the DG check naming this module.
+PwgElementDev AssemblyManager::pwgStepArgs(const double *u, const double *lambda) {
+  requireReady(false);
+  porousWeakGalerkin *pm = dynamic_cast<porousWeakGalerkin *>(physics_.get());
+  MHA_REQUIRE(pm != nullptr, MHA_ERR_INVALID, "the block's physics module is not porousWeakGalerkin");
+  MHA_REQUIRE(lambda != nullptr, MHA_ERR_INVALID, "null trace values");
+  MHA_REQUIRE(!time_.transient, MHA_ERR_INVALID,
+              "porousWeakGalerkin: the element step is a steady residual (the module has no time-derivative term); the "
+              "context is transient");
+  if (!pmh_dg_checked_) {
+    check_dg_lids(nelem_, n_, nrows_, h_lids_.data(), "porousWeakGalerkin");
+    pmh_dg_checked_ = true;
+  }
+  bindState(u, nullptr, nullptr);
+  prepareSideTables();
+  PwgElementDev a = pm->elementArgs();
+  a.lambda = lambda;
+  a.orient = has_orient_ ? d_orient_.data() : nullptr;
+  return a;
+}
+
+void AssemblyManager::pwgElementBlocks(const double *u, const double *lambda, double *res, double *blocks) {
+  MHA_REQUIRE(res || blocks, MHA_ERR_INVALID, "no output requested");
+  PwgElementDev a = pwgStepArgs(u, lambda);
+  a.res = res;
+  a.blocks = blocks;
+  timedBegin();
+  launch_porous_wg_blocks(blockDev(), sideTablesDev(), a, time_, stream_);
+  timedEnd();
+}
+
+void AssemblyManager::pwgCondensedElement(const double *u, const double *lambda, double *schur, double *gvec, double *du,
+                                          int32_t *num_singular) {
+  MHA_REQUIRE(schur || gvec || du, MHA_ERR_INVALID, "no output requested");
+  PwgElementDev a = pwgStepArgs(u, lambda);
+  a.schur = schur;
+  a.gvec = gvec;
+  a.du = du;
+  a.singular = num_singular;
+  timedBegin();
+  launch_porous_wg_fused(blockDev(), sideTablesDev(), a, time_, stream_);
   timedEnd();
 }
 

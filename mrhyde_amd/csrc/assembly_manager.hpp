@@ -84,6 +84,9 @@ class AssemblyManager {
   // uncondensed block by the plain kernel; geometry, local matrices, interior solve and Schur complement in one launch
   void pmhElementBlocks(const double *u, const double *lambda, double *res, double *blocks);
   void pmhCondensedElement(const double *u, const double *lambda, double *schur, double *gvec, double *du, int32_t *num_singular);
+  // the element step of porousWeakGalerkin (kernels/porous_wg_blocks.hip, kernels/porous_wg_fused.hip), as the pair above
+  void pwgElementBlocks(const double *u, const double *lambda, double *res, double *blocks);
+  void pwgCondensedElement(const double *u, const double *lambda, double *schur, double *gvec, double *du, int32_t *num_singular);
   void scatterLocal(const double *local_J, const double *local_res, double *res, double *crs_vals);
   // boundary groups (reference: src/tools/boundaryGroup.hpp, assemblyManager.cpp:2518-2638)
   int addBoundaryGroup(const std::string &sidename, int bc_type, int num, const int32_t *elem_ids,
@@ -155,6 +158,8 @@ class AssemblyManager {
   // tables, the kernels' arguments without their outputs
   PmhElementDev pmhStepArgs(const double *u, const double *lambda);
   bool pmh_dg_checked_ = false;
+  // the same setup for the two porousWeakGalerkin element steps (the DG check is shared: one module per block)
+  PwgElementDev pwgStepArgs(const double *u, const double *lambda);
   void timedBegin();
   void timedEnd();
 

@@ -558,6 +558,31 @@ int mha_pmh_condensed_element(mha_context *ctx, const double *u, const double *l
   return guarded([&] { mgr(ctx).pmhCondensedElement(u, lambda, schur, gvec, du, num_singular); });
 }
 
+int mha_pwg_element_blocks(mha_context *ctx, const double *u, const double *lambda, double *res, double *blocks) {
+  return guarded([&] { mgr(ctx).pwgElementBlocks(u, lambda, res, blocks); });
+}
+
+int mha_pwg_condensed_element(mha_context *ctx, const double *u, const double *lambda, double *schur, double *gvec,
+                              double *du, int32_t *num_singular) {
+  return guarded([&] { mgr(ctx).pwgCondensedElement(u, lambda, schur, gvec, du, num_singular); });
+}
+
+int mha_mesh_porous_weak_galerkin_sizes(int dim, const int *ncell, int *nelem, int64_t *ndof, int64_t *ntrace) {
+  return guarded([&] {
+    MHA_REQUIRE(ncell && nelem && ndof && ntrace, MHA_ERR_INVALID, "null argument");
+    mha::mesh_porous_weak_galerkin_sizes(dim, ncell, nelem, ndof, ntrace);
+  });
+}
+
+int mha_mesh_porous_weak_galerkin(int dim, const int *ncell, const double *lo, const double *hi, double *nodes, int32_t *lids,
+                                  int32_t *offsets, int8_t *orient, int32_t *trace_lids, uint8_t *trace_side) {
+  return guarded([&] {
+    MHA_REQUIRE(ncell && lo && hi && nodes && lids && offsets && orient && trace_lids && trace_side, MHA_ERR_INVALID,
+                "null argument");
+    mha::mesh_porous_weak_galerkin(dim, ncell, lo, hi, nodes, lids, offsets, orient, trace_lids, trace_side);
+  });
+}
+
 int mha_mesh_porous_hybrid_sizes(int dim, const int *ncell, int *nelem, int64_t *ndof, int64_t *ntrace) {
   return guarded([&] {
     MHA_REQUIRE(ncell && nelem && ndof && ntrace, MHA_ERR_INVALID, "null argument");

@@ -378,6 +378,23 @@ struct PmhElementDev {
   int *singular = nullptr;         //               += 1 per element with a non-positive pivot
 };
 
+// The element step of porousWeakGalerkin (kernels/porous_wg_blocks.hip, kernels/porous_wg_fused.hip).  Unknowns of an
+// element: pint, the 2 dim dofs of u, the 2 dim dofs of t (dof 2 c + s), then the 2 dim traces in HFACE order;
+// n_int = 1 + 4 dim, n = 1 + 6 dim.
+struct PwgElementDev {
+  const double *lambda = nullptr;  // [E][2 dim] trace unknowns, HFACE face order
+  const int8_t *orient = nullptr;  // [E][n_int] basis signs in (variable, dof) order, or null
+  FuncDesc f[2];                   // source, perm at the volume points
+  const double *edata = nullptr;   // [E][ecols]: perm = column 0 ("use permeability data"); null: the function
+  int ecols = 0;
+  double *res = nullptr;           // plain kernel: [E][n] -res.val()
+  double *blocks = nullptr;        //               [E][n][n] res(r).dx(c), stored
+  double *schur = nullptr;         // fused kernel: [E][2 dim][2 dim], [E][2 dim], [E][n_int] as condense.hip defines them
+  double *gvec = nullptr;
+  double *du = nullptr;
+  int *singular = nullptr;         //               += 1 per element with a non-positive pivot or sigma
+};
+
 // Row blocks keyed by assembly pattern (block_pattern.hpp) for the matrix-core row-owner Jacobian.
 struct BlockPatternDev {
   int num_wgs = 0, max_w_doubles = 0;

@@ -44,13 +44,15 @@ constexpr int kProductMaxWaves = 8;
   X(3, MHA_PHYSICS_NAVIERSTOKES_CDR)          \
   X(2, MHA_PHYSICS_HELMHOLTZ)                 \
   X(3, MHA_PHYSICS_HELMHOLTZ)                 \
+  X(2, MHA_PHYSICS_POROUS_WEAK_GALERKIN)      \
+  X(3, MHA_PHYSICS_POROUS_WEAK_GALERKIN)      \
   X(2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED)
 
 // f(integral_constant<int, DIM>, integral_constant<int, PHYS>) for the pair (dim, |physics|); refuses any other pair
 // with "no <what> kernel for physics ...".  physics < 0 is the engine's mass mode of module -physics.
 template <class F>
 void dispatch_module(int dim, int physics, const char *what, F &&f) {
-  static_assert(MHA_PHYSICS_HELMHOLTZ < 100, "the switch key holds two decimal digits of module id");
+  static_assert(MHA_PHYSICS_HELMHOLTZ < 100 && MHA_PHYSICS_POROUS_WEAK_GALERKIN < 100, "the switch key holds two decimal digits of module id");
 #define MHA_MODULE_CASE(D, P) \
   case D * 100 + P: f(std::integral_constant<int, D>{}, std::integral_constant<int, P>{}); break;
   switch (dim * 100 + (physics < 0 ? -physics : physics)) {
@@ -80,7 +82,8 @@ constexpr bool has_field_form() {
 // f(integral_constant<int, EXPR>) with the variant of the point function that pp asks for: 2 deck strings that read
 // the solution fields / 3 porousMixed with heterogeneous permeability / 1 deck strings / 0 plain.  Deck strings count
 // for a module only (physics > 0): the engine's mass mode evaluates none.  f is instantiated with the variants the
-// module has, no others.
+// module has, no others.  porousWeakGalerkin reads its element data at run time inside variants 0 and 1 (one test of a
+// kernel argument per point), so it carries element data and deck strings together and has no variant of its own.
 template <int PHYS, class F>
 void dispatch_expr(const PhysParamsDev &pp, F &&f) {
   const bool module = pp.physics > 0;

@@ -84,6 +84,13 @@ struct Layout<MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED, DIM> {
   __host__ __device__ static constexpr int type(int) { return MHA_BASIS_HGRAD; }
 };
 
+// porousWeakGalerkin: pint, u, t (pbndry, the HFACE trace, is data of the element step)
+template <int DIM>
+struct Layout<MHA_PHYSICS_POROUS_WEAK_GALERKIN, DIM> {
+  static constexpr int nvars = 3, NS = 3 + 2 * DIM;
+  __host__ __device__ static constexpr int type(int v) { return v == 0 ? MHA_BASIS_HVOL : MHA_BASIS_HDIV; }
+};
+
 __host__ __device__ constexpr int slots_of(int type, int dim) { return type == MHA_BASIS_HVOL ? 1 : 1 + dim; }
 // slots that carry a time derivative: every value, not gradients / divergence
 __host__ __device__ constexpr bool value_like(int type, int s, int dim) {
@@ -315,5 +322,6 @@ constexpr int geo_size() { return 2 * DIM * DIM + 2 + DIM; }  // J, Ji, det, w, 
     else if constexpr (PHYS == MHA_PHYSICS_CDR) cdr_point<DIM, EXPR>(pa, F);                                             \
     else if constexpr (PHYS == MHA_PHYSICS_NAVIERSTOKES_CDR) navierstokes_cdr_point<DIM, EXPR>(pa, F);                   \
     else if constexpr (PHYS == MHA_PHYSICS_HELMHOLTZ) helmholtz_point<DIM, (EXPR != 0)>(pa, F);                          \
+    else if constexpr (PHYS == MHA_PHYSICS_POROUS_WEAK_GALERKIN) porous_wg_point<DIM, (EXPR != 0)>(pa, F);               \
     else navierstokes_point<DIM, (EXPR != 0)>(pa, F);                                                                    \
   } while (0)

@@ -204,6 +204,13 @@ void launch_porous_hybrid_blocks(const BlockDev &b, const SideTablesDev &st, con
                                  hipStream_t stream);
 void launch_porous_hybrid_fused(const BlockDev &b, const SideTablesDev &st, const PmhElementDev &a, const TimeDev &tm,
                                 hipStream_t stream);
+// porous_wg_blocks.hip: the uncondensed element block of porousWeakGalerkin (a.res, a.blocks), plain and unfused;
+// porous_wg_fused.hip: the same step with the closed-form interior solve and the Schur complement inside, one thread per
+// element (a.schur, a.gvec, a.du, 16-byte aligned; a.singular)
+void launch_porous_wg_blocks(const BlockDev &b, const SideTablesDev &st, const PwgElementDev &a, const TimeDev &tm,
+                             hipStream_t stream);
+void launch_porous_wg_fused(const BlockDev &b, const SideTablesDev &st, const PwgElementDev &a, const TimeDev &tm,
+                            hipStream_t stream);
 void launch_condense(int n_int, int n_trace, int64_t nelem, const double *blocks, const double *res, double *schur,
                      double *gvec, double *du, int *singular, hipStream_t stream);
 

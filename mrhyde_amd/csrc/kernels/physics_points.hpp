@@ -93,6 +93,26 @@ __device__ __forceinline__ void porous_point(const PointArgs<DIM> &a, Dual *F) {
   F[1 + DIM] = -p;  // -(p, div v)
 }
 
+// porousWeakGalerkin (reference: src/physics/porousWeakGalerkin.cpp:94-323); myvars of the block {pint (HVOL), u (HDIV),
+// t (HDIV)}; slots pint, u_x.., div u, t_x.., div t; functions {source, perm}.  With element data ("use permeability
+// data", updatePerm :601-609) perm = data(elem, 0): the value itself, not its inverse as in porousMixed.  The data
+// pointer is a kernel argument, so the test is wave-uniform and the same instantiation carries deck strings beside it.
+template <int DIM, bool EXPR>
+__device__ __forceinline__ void porous_wg_point(const PointArgs<DIM> &a, Dual *F) {
+  const PhysParamsDev &pp = *a.pp;
+  const double src = eval_func<DIM, EXPR>(pp.f[0], a.e, a.q, a.nq, a.x);
+  const double perm = pp.het.edata ? pp.het.edata[(size_t)a.e * pp.het.ecols] : eval_func<DIM, EXPR>(pp.f[1], a.e, a.q, a.nq, a.x);
+  constexpr int U0 = 1, T0 = 2 + DIM;
+  F[0] = a.U[T0 + DIM] - src;  // (div t - source, q)
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    F[U0 + d] = a.U[U0 + d];                         // (u, v)
+    F[T0 + d] = a.U[U0 + d] * perm + a.U[T0 + d];  // (perm u + t, s)
+  }
+  F[U0 + DIM] = a.U[0];  // (pint, div v)
+  F[T0 + DIM] = mk(0.0);
+}
+
 // navierstokes (reference: src/physics/navierstokes.cpp:82-849, computeTau :1054-1079); myvars {ux, pr, uy[, uz]};
 // functions {source ux, source pr, source uy, source uz, density, viscosity}; p = {useSUPG, usePSPG, fix_uz_offsets}
 template <int DIM, bool EXPR>

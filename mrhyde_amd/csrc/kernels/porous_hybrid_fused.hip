@@ -31,35 +31,13 @@
 #include "launch.hpp"
 #include "porous_hybrid.hpp"
 #include "side_geometry.hpp"
+#include "stream_rows.hpp"
 
 namespace mha {
 namespace {
 
 constexpr int kPmhWaves = 4;  // wavefronts (of 64 elements) per workgroup
-
-__device__ __forceinline__ void pmh_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// rows of W doubles, one per lane, staged at stride W | 1 in sb -> out[0 .. cnt W) in 16-byte pieces (out 16-byte aligned)
-template <int W>
-__device__ __forceinline__ void pmh_stream_rows(double *out, const double *sb, int lane, int cnt) {
-  constexpr int WP = W | 1;
-  const int total = cnt * W;
-  for (int i = 2 * lane; i + 1 < total; i += 128) {
-    const int r0 = i / W, r1 = (i + 1) / W;
-    double2 v;
-    v.x = sb[r0 * WP + (i - r0 * W)];
-    v.y = sb[r1 * WP + (i + 1 - r1 * W)];
-    *reinterpret_cast<double2 *>(out + i) = v;
-  }
-  if ((total & 1) && lane == 0) {
-    const int i = total - 1, r0 = i / W;
-    out[i] = sb[r0 * WP + (i - r0 * W)];
-  }
-}
+// (pmh_wave_sync, pmh_stream_rows: stream_rows.hpp, shared with porous_wg_fused.hip)
 
 template <int DIM, bool EXPR>
 __global__ __launch_bounds__(64 * kPmhWaves) void porous_hybrid_fused_kernel(BlockDev b, SideTablesDev st, PmhElementDev a, TimeDev tm) {

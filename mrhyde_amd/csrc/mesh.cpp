@@ -429,6 +429,31 @@ void mesh_porous_hybrid(int dim, const int *nc, const double *lo, const double *
   }
 }
 
+void mesh_porous_weak_galerkin_sizes(int dim, const int *nc, int *nelem, int64_t *ndof, int64_t *ntrace) {
+  mesh_porous_hybrid_sizes(dim, nc, nelem, ndof, ntrace);
+  MHA_REQUIRE(static_cast<int64_t>(*nelem) * (1 + 4 * dim) < (int64_t{1} << 31), MHA_ERR_INVALID,
+              "porous weak Galerkin mesh: too many elements for 32-bit LIDs");
+  *ndof = static_cast<int64_t>(*nelem) * (1 + 4 * dim);
+}
+
+void mesh_porous_weak_galerkin(int dim, const int *nc, const double *lo, const double *hi, double *nodes, int32_t *lids,
+                               int32_t *offsets, int8_t *orient, int32_t *trace_lids, uint8_t *trace_side) {
+  int nelem;
+  int64_t ndof, ntrace;
+  mesh_porous_weak_galerkin_sizes(dim, nc, &nelem, &ndof, &ntrace);
+  // vertices, traces and face signs are those of the porousMixedHybridized mesh (p, u); t repeats u's signs
+  const int nu = 2 * dim, nh = 1 + nu, ni = 1 + 2 * nu;
+  std::vector<int32_t> hlids(static_cast<size_t>(nelem) * nh), hoffs(nh);
+  std::vector<int8_t> horient(static_cast<size_t>(nelem) * nh);
+  mesh_porous_hybrid(dim, nc, lo, hi, nodes, hlids.data(), hoffs.data(), horient.data(), trace_lids, trace_side);
+  for (int k = 0; k < ni; ++k) offsets[k] = k;
+  for (int e = 0; e < nelem; ++e)
+    for (int k = 0; k < ni; ++k) {
+      lids[static_cast<size_t>(e) * ni + k] = e * ni + k;
+      orient[static_cast<size_t>(e) * ni + k] = horient[static_cast<size_t>(e) * nh + (k < nh ? k : k - nu)];
+    }
+}
+
 void check_swhdg_subgrids(int m, int nelem, int nrows, const double *nodes, const int32_t *lids, const int32_t *offs) {
   MHA_REQUIRE(m >= 1 && m <= 4, MHA_ERR_INVALID,
               "HDG subgrids: m = " << m << " sub-elements per direction is outside 1..4 (the dense interior solve holds n_int = 3 (m+1)^2 <= 75 unknowns in LDS)");

@@ -41,6 +41,13 @@ void mesh_porous_hybrid_sizes(int dim, const int *nc, int *nelem, int64_t *ndof,
 void mesh_porous_hybrid(int dim, const int *nc, const double *lo, const double *hi, double *nodes, int32_t *lids,
                         int32_t *offsets, int8_t *orient, int32_t *trace_lids, uint8_t *trace_side);
 
+// Mesh of a porousWeakGalerkin block (mha_mesh_porous_weak_galerkin): nodes, trace_lids, trace_side and ntrace are
+// mesh_porous_hybrid's; the DG unknowns are pint, u, t (lids[e][k] = e (1 + 4 dim) + k, offsets the identity), and u and
+// t carry the same face signs in orient[E][1 + 4 dim].
+void mesh_porous_weak_galerkin_sizes(int dim, const int *nc, int *nelem, int64_t *ndof, int64_t *ntrace);
+void mesh_porous_weak_galerkin(int dim, const int *nc, const double *lo, const double *hi, double *nodes, int32_t *lids,
+                               int32_t *offsets, int8_t *orient, int32_t *trace_lids, uint8_t *trace_side);
+
 // The layout check of mha_swhdg_set_subgrids (throws MHA_ERR_INVALID): elements [k m^2, (k+1) m^2) are macro element k's
 // m x m sub-mesh, row-major with x fastest; its rows are shared only inside k with the Q1 connectivity of an m x m grid;
 // its vertices are the bilinear image of the uniform subdivision of the macro quad to 1e-12 x its size.  m in 1..4.

@@ -94,7 +94,7 @@ PmhElementDev porousMixedHybridized::elementArgs(int dim) {
   return a;
 }
 
-void check_dg_lids(int nelem, int n, int nrows, const int32_t *lids) {
+void check_dg_lids(int nelem, int n, int nrows, const int32_t *lids, const char *module) {
   MHA_REQUIRE(nelem > 0 && n > 0 && nrows > 0 && lids, MHA_ERR_INVALID, "DG check: null or empty LID map");
   std::vector<int32_t> owner(static_cast<size_t>(nrows), -1);
   for (int e = 0; e < nelem; ++e)
@@ -102,7 +102,7 @@ void check_dg_lids(int nelem, int n, int nrows, const int32_t *lids) {
       const int32_t row = lids[static_cast<size_t>(e) * n + k];
       MHA_REQUIRE(row >= 0 && row < nrows, MHA_ERR_INVALID, "DG check: LID out of range: " << row);
       MHA_REQUIRE(owner[row] < 0, MHA_ERR_INVALID,
-                  "porousMixedHybridized: row " << row << " belongs to elements " << owner[row] << " and " << e
+                  module << ": row " << row << " belongs to elements " << owner[row] << " and " << e
                       << ": the block's LIDs must be DG (every LID in exactly one element); a conforming HDIV map is porousMixed's");
       owner[row] = e;
     }

@@ -35,7 +35,7 @@ class porousMixedHybridized : public porousMixed {
 };
 
 // every LID of lids[nelem][n] lies in [0, nrows) and belongs to exactly one (element, position); MHA_ERR_INVALID names
-// the first row that two elements share (a conforming HDIV map)
-void check_dg_lids(int nelem, int n, int nrows, const int32_t *lids);
+// the first row that two elements share (a conforming HDIV map) and the module that asks (porousWeakGalerkin shares the check)
+void check_dg_lids(int nelem, int n, int nrows, const int32_t *lids, const char *module = "porousMixedHybridized");
 
 }  // namespace mha

@@ -5,6 +5,7 @@
 #include "cdr.hpp"
 #include "helmholtz.hpp"
 #include "porous_hybrid.hpp"
+#include "porous_weak_galerkin.hpp"
 
 #include "expression.hpp"
 #include "porous_data.hpp"
@@ -594,6 +595,7 @@ std::unique_ptr<PhysicsBase> import_physics(int physics_id, int dim) {
   if (physics_id == MHA_PHYSICS_NAVIERSTOKES) p.reset(new navierstokes(dim));
   if (physics_id == MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED) p.reset(new shallowwaterHybridized());
   if (physics_id == MHA_PHYSICS_POROUS_MIXED_HYBRIDIZED) p.reset(new porousMixedHybridized());
+  if (physics_id == MHA_PHYSICS_POROUS_WEAK_GALERKIN) p.reset(new porousWeakGalerkin());
   MHA_REQUIRE(p != nullptr, MHA_ERR_INVALID, "unknown physics module id " << physics_id);
   p->id = physics_id;
   return p;
