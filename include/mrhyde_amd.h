@@ -238,6 +238,38 @@ int mha_get_graph(mha_context *ctx, int32_t *rowptr_host, int32_t *colind_host);
  * MHA_PATH_ROW_OWNER, a transient state in the element step.  Not built: triangles and tetrahedra, the multiscale
  * interface / "aux pbndry" coupling.  (id 13; 11 stays unassigned, see above) */
 #define MHA_PHYSICS_POROUS_WEAK_GALERKIN (MHA_PHYSICS_LINEARELASTICITY_THERMAL + 6)
+/* stokes (src/physics/stokes.cpp): ux, pr, uy[, uz], all HGRAD, in that order (:25-41), each with its own order (Q1/Q1
+ * with PSPG, Q2/Q1 without), 2-D and 3-D.  Volume terms (:178-438): momentum row i gets -"source u<i>" against the test
+ * value and viscosity d_d u_i - delta_id pr against its d-th derivative; the pr row gets div u against the test value.
+ * Parameter "usePSPG" (0; :45) adds tau (d_d pr + source_d) against the d-th derivative of the pr test function, with
+ * tau = h / (2 viscosity) in 2-D (:256; the h^2 line is commented out there) and h^2 / (2 viscosity) in 3-D (:402);
+ * "useLSIC" (0; :44) adds h^2 / (2 viscosity) div u against the SUM of the derivatives of the pr test function (:283,
+ * :432).  h is Workset::getElementSize.  No time-derivative term.  Functions (:58-62): "source ux", "source pr", "source
+ * uy", "source uz" (0), "viscosity" (1): constants, arrays, closed forms or deck strings in the coordinates; "source pr"
+ * is registered and evaluated and read by no term.  boundaryResidual and computeFlux are empty in the reference
+ * (:444-456): boundary groups on the block add nothing, mha_compute_flux returns zeros.  The variable layout is
+ * navierstokes': every element shape of that module runs, the 3-D Q2/Q1 element included.  Runs on the point engine
+ * (MHA_PATH_AUTO / _ROW_GATHER / _POINT_ENGINE / _LOCAL_THEN_SCATTER) and in the matrix-free products.  Refused with
+ * MHA_ERR_INVALID: MHA_PATH_ROW_OWNER, MHA_ASSEMBLE_DETERMINISTIC, deck strings that read the solution fields, 1-D.
+ * (id 14) */
+#define MHA_PHYSICS_STOKES (MHA_PHYSICS_LINEARELASTICITY_THERMAL + 7)
+/* shallowwater, the continuous-Galerkin shallow water module (src/physics/shallowwater.cpp): H, Hu, Hv, all HGRAD, in
+ * that order (:24-29), 2-D only.  The variable H holds the surface elevation xi; the depth is D = xi + bathymetry.
+ * Volume terms (:118-153):
+ *   row H:  xi_t - "source H"                                  against the test value, (-Hu, -Hv) against its gradient;
+ *   row Hu: Hu_t - gravity xi bathymetry_x - "source Hu"       against the test value,
+ *           (-(Hu^2 / D + gravity (D^2 - bathymetry^2) / 2), -Hu Hv / D)          against its gradient;
+ *   row Hv: the mirror image with bathymetry_y and "source Hv".
+ * A dry point (D = 0) divides by zero as in the reference.  Functions (:47-62): "bathymetry" (1), "bathymetry_x" (0),
+ * "bathymetry_y" (0), "source H", "source Hu", "source Hv" (0): constants, arrays, closed forms or deck strings in the
+ * coordinates.  "viscosity" (0) and "Coriolis" (0) are evaluated by the reference (:79-80) and read by no term;
+ * "bottom friction" (1), "flux left|right|top|bottom", "Neumann source Hu|Hv" (0) and "bathymetry side" are registered and
+ * never evaluated: all are accepted and unread here.  Parameters: "gravity" (9.8; :32 -- not shallowwaterHybridized's
+ * g = 9.81) and "form_param" (accepted, unused; :34).  boundaryResidual and computeFlux are empty in the reference
+ * (:161-174): boundary groups add nothing, mha_compute_flux returns zeros.  Runs on the point engine and in the
+ * matrix-free products.  Refused with MHA_ERR_INVALID: 3-D and 1-D, MHA_PATH_ROW_OWNER, MHA_ASSEMBLE_DETERMINISTIC, deck
+ * strings that read the solution fields.  (id 15) */
+#define MHA_PHYSICS_SHALLOWWATER (MHA_PHYSICS_LINEARELASTICITY_THERMAL + 8)
 int mha_physics_select(mha_context *ctx, int physics_id);
 #define MHA_FUNC_CONSTANT 0
 #define MHA_FUNC_IP_ARRAY 1     /* dev pointer to [E][numip] f64                    */

@@ -68,8 +68,12 @@ ALL_PHYSICS_IDS = dict(PHYSICS_IDS, helmholtz=PHYSICS_HELMHOLTZ)
 PHYSICS_POROUS_MIXED_HYBRIDIZED = 12
 # porousWeakGalerkin: pint (HVOL), u, t (HDIV-DG) on the block, the trace pbndry (HFACE) as data per element
 PHYSICS_POROUS_WEAK_GALERKIN = 13
+# stokes: ux, pr, uy[, uz] (HGRAD), optional PSPG / LSIC; shallowwater: H, Hu, Hv (HGRAD, 2-D), continuous Galerkin
+PHYSICS_STOKES = 14
+PHYSICS_SHALLOWWATER = 15
 MODULE_IDS = dict(ALL_PHYSICS_IDS, porousMixedHybridized=PHYSICS_POROUS_MIXED_HYBRIDIZED,
-                  porousWeakGalerkin=PHYSICS_POROUS_WEAK_GALERKIN)
+                  porousWeakGalerkin=PHYSICS_POROUS_WEAK_GALERKIN, stokes=PHYSICS_STOKES,
+                  shallowwater=PHYSICS_SHALLOWWATER)
 PATH_POINT_ENGINE = 4
 PATH_ROW_GATHER = 5
 BC_NEUMANN, BC_WEAK_DIRICHLET, BC_FLUX = 1, 2, 3

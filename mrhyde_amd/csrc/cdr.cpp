@@ -20,8 +20,10 @@ void define_cdr_functions(FunctionManager &fm) {
     if (!fm.has(k)) fm.addFunction(k, constant(1.0));
 }
 
-// navierstokes::computeFlux and cdr::computeFlux are empty (navierstokes.cpp:1016-1018, cdr.cpp:161-164): the flux view
-// keeps the zeros the workset reset left in it
+}  // namespace
+
+// navierstokes::computeFlux and cdr::computeFlux are empty (navierstokes.cpp:1016-1018, cdr.cpp:161-164), as are those of
+// stokes and shallowwater: the flux view keeps the zeros the workset reset left in it
 void zero_flux(Workset &w) {
   MHA_REQUIRE(w.bnd.flux != nullptr, MHA_ERR_INVALID, "computeFlux: no flux array on the workset");
   const size_t npt = static_cast<size_t>(w.bnd.num) * w.side_tables.nqs;
@@ -29,8 +31,6 @@ void zero_flux(Workset &w) {
   if (w.bnd.dflux_du) MHA_HIP(hipMemsetAsync(w.bnd.dflux_du, 0, sizeof(double) * npt * w.dev.n, w.stream));
   if (w.bnd.dflux_daux) MHA_HIP(hipMemsetAsync(w.bnd.dflux_daux, 0, sizeof(double) * npt, w.stream));
 }
-
-}  // namespace
 
 cdr::cdr() {
   label = "cdr";

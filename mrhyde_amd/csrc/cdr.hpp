@@ -4,6 +4,9 @@
 
 namespace mha {
 
+// computeFlux of a module whose flux is empty in the reference: zeros in the workset's flux views
+void zero_flux(Workset &w);
+
 // cdr: c_t + v . grad c - div(diffusion / (density specific heat) grad c) + reaction = source
 // (reference: src/physics/cdr.hpp, src/physics/cdr.cpp:15-142); myvars {c} (:22-23), 2-D and 3-D.  Volume terms on the
 // point engine (cdr_point).  Every function may read the solution fields ("reaction: 0.5*c*c"): the engine then runs the

@@ -24,7 +24,7 @@ namespace {
 constexpr size_t kPointLdsLimit = 160 * 1024;
 constexpr int kProductMaxWaves = 8;
 
-// every (dimension, module) pair with a point function; shallowwaterHybridized is 2-D only
+// every (dimension, module) pair with a point function; shallowwaterHybridized and shallowwater are 2-D only
 #define MHA_POINT_MODULES(X)                  \
   X(2, MHA_PHYSICS_THERMAL)                   \
   X(3, MHA_PHYSICS_THERMAL)                   \
@@ -46,13 +46,18 @@ constexpr int kProductMaxWaves = 8;
   X(3, MHA_PHYSICS_HELMHOLTZ)                 \
   X(2, MHA_PHYSICS_POROUS_WEAK_GALERKIN)      \
   X(3, MHA_PHYSICS_POROUS_WEAK_GALERKIN)      \
-  X(2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED)
+  X(2, MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED)   \
+  X(2, MHA_PHYSICS_STOKES)                    \
+  X(3, MHA_PHYSICS_STOKES)                    \
+  X(2, MHA_PHYSICS_SHALLOWWATER)
 
 // f(integral_constant<int, DIM>, integral_constant<int, PHYS>) for the pair (dim, |physics|); refuses any other pair
 // with "no <what> kernel for physics ...".  physics < 0 is the engine's mass mode of module -physics.
 template <class F>
 void dispatch_module(int dim, int physics, const char *what, F &&f) {
-  static_assert(MHA_PHYSICS_HELMHOLTZ < 100 && MHA_PHYSICS_POROUS_WEAK_GALERKIN < 100, "the switch key holds two decimal digits of module id");
+  static_assert(MHA_PHYSICS_HELMHOLTZ < 100 && MHA_PHYSICS_POROUS_WEAK_GALERKIN < 100 && MHA_PHYSICS_STOKES < 100 &&
+                    MHA_PHYSICS_SHALLOWWATER < 100,
+                "the switch key holds two decimal digits of module id");
 #define MHA_MODULE_CASE(D, P) \
   case D * 100 + P: f(std::integral_constant<int, D>{}, std::integral_constant<int, P>{}); break;
   switch (dim * 100 + (physics < 0 ? -physics : physics)) {

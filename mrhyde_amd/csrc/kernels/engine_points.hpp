@@ -91,6 +91,20 @@ struct Layout<MHA_PHYSICS_POROUS_WEAK_GALERKIN, DIM> {
   __host__ __device__ static constexpr int type(int v) { return v == 0 ? MHA_BASIS_HVOL : MHA_BASIS_HDIV; }
 };
 
+// stokes: ux, pr, uy[, uz] -- navierstokes' layout
+template <int DIM>
+struct Layout<MHA_PHYSICS_STOKES, DIM> {
+  static constexpr int nvars = 1 + DIM, NS = (1 + DIM) * (1 + DIM);
+  __host__ __device__ static constexpr int type(int) { return MHA_BASIS_HGRAD; }
+};
+
+// shallowwater: H, Hu, Hv
+template <int DIM>
+struct Layout<MHA_PHYSICS_SHALLOWWATER, DIM> {
+  static constexpr int nvars = 3, NS = 3 * (1 + DIM);
+  __host__ __device__ static constexpr int type(int) { return MHA_BASIS_HGRAD; }
+};
+
 __host__ __device__ constexpr int slots_of(int type, int dim) { return type == MHA_BASIS_HVOL ? 1 : 1 + dim; }
 // slots that carry a time derivative: every value, not gradients / divergence
 __host__ __device__ constexpr bool value_like(int type, int s, int dim) {
@@ -323,5 +337,7 @@ constexpr int geo_size() { return 2 * DIM * DIM + 2 + DIM; }  // J, Ji, det, w, 
     else if constexpr (PHYS == MHA_PHYSICS_NAVIERSTOKES_CDR) navierstokes_cdr_point<DIM, EXPR>(pa, F);                   \
     else if constexpr (PHYS == MHA_PHYSICS_HELMHOLTZ) helmholtz_point<DIM, (EXPR != 0)>(pa, F);                          \
     else if constexpr (PHYS == MHA_PHYSICS_POROUS_WEAK_GALERKIN) porous_wg_point<DIM, (EXPR != 0)>(pa, F);               \
+    else if constexpr (PHYS == MHA_PHYSICS_STOKES) stokes_point<DIM, (EXPR != 0)>(pa, F);                                \
+    else if constexpr (PHYS == MHA_PHYSICS_SHALLOWWATER) shallowwater_point<DIM, (EXPR != 0)>(pa, F);                    \
     else navierstokes_point<DIM, (EXPR != 0)>(pa, F);                                                                    \
   } while (0)

@@ -469,4 +469,97 @@ __device__ __forceinline__ void swhdg_point(const PointArgs<DIM> &a, Dual *F) {
   }
 }
 
+// stokes (reference: src/physics/stokes.cpp:178-438); myvars {ux, pr, uy[, uz]}; functions {source ux, source uy,
+// source uz, viscosity} -- "source pr" is registered and evaluated by the reference (:59, :78) and read by no term: it is
+// not in the table; p = {usePSPG, useLSIC}.
+//   momentum row i   value slot -source_i; gradient slot d  viscosity d_d u_i - delta_id pr
+//   pr row           value slot div u
+//   usePSPG          gradient slot d of the pr row += tau (d_d pr + source_d), tau = h / (2 viscosity) in 2-D (:256; the
+//                    line with h^2 is commented out there) and h^2 / (2 viscosity) in 3-D (:402)
+//   useLSIC          EVERY gradient slot of the pr row += h^2 / (2 viscosity) div u: the reference tests with
+//                    d_x q + d_y q [+ d_z q] (:283, :432)
+// kept as they are: the reference's gold depends on them.  No time-derivative term: a transient call scales the
+// operator by alpha_u through the seeding.  The uz rows use their own offsets (:353).  a.h is Workset::getElementSize.
+// EXPR: deck strings in the coordinates, evaluated in a loop that is NOT unrolled (one inlined interpreter).
+template <int DIM, bool EXPR>
+__device__ __forceinline__ void stokes_point(const PointArgs<DIM> &a, Dual *F) {
+  static_assert(DIM >= 2, "");
+  constexpr int S = 1 + DIM, NF = DIM + 1;  // slots per HGRAD variable; functions read
+  constexpr int vnum[3] = {0, 2, 3}, prnum = 1;
+  const PhysParamsDev &pp = *a.pp;
+  double fv[NF];  // source_0 .. source_{DIM-1}, viscosity
+  if constexpr (EXPR) {
+#pragma nounroll
+    for (int k = 0; k < NF; ++k) fv[k] = eval_func<DIM, true>(pp.f[k], a.e, a.q, a.nq, a.x);
+  } else {
+#pragma unroll
+    for (int k = 0; k < NF; ++k) fv[k] = eval_func<DIM, false>(pp.f[k], a.e, a.q, a.nq, a.x);
+  }
+  const double visc = fv[DIM];
+  const Dual pr = a.U[prnum * S];
+  Dual divu = mk(0.0);
+#pragma unroll
+  for (int i = 0; i < DIM; ++i) {
+    const int b = vnum[i] * S;
+    F[b] = mk(-fv[i]);
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) {
+      F[b + 1 + d] = a.U[b + 1 + d] * visc;
+      if (d == i) F[b + 1 + d] -= pr;
+    }
+    divu += a.U[b + 1 + i];
+  }
+  F[prnum * S] = divu;
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) F[prnum * S + 1 + d] = mk(0.0);
+  if (pp.p[0] != 0.0) {
+    const double tau = (DIM == 2 ? a.h : a.h * a.h) / (2.0 * visc);
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) F[prnum * S + 1 + d] += (a.U[prnum * S + 1 + d] + fv[d]) * tau;
+  }
+  if (pp.p[1] != 0.0) {
+    const Dual s = divu * (a.h * a.h / (2.0 * visc));
+#pragma unroll
+    for (int d = 0; d < DIM; ++d) F[prnum * S + 1 + d] += s;
+  }
+}
+
+// shallowwater, continuous Galerkin (reference: src/physics/shallowwater.cpp:118-153); myvars {H, Hu, Hv} (2-D);
+// functions {bathymetry, bathymetry_x, bathymetry_y, source H, source Hu, source Hv}; p = {gravity}.  The variable H
+// holds the surface elevation xi, the depth is D = xi + bathymetry:
+//   row H    value slot xi_t - source H;                          gradient slots (-Hu, -Hv)
+//   row Hu   value slot Hu_t - g xi bathymetry_x - source Hu;     gradient slots (-(Hu^2/D + g (D D - b b) / 2), -Hu Hv / D)
+//   row Hv   the mirror image
+// D D - b b is kept as the reference writes it (:137, :145); a dry point (D = 0) divides by zero as there.  "viscosity"
+// and "Coriolis" are evaluated by the reference (:79-80) and read by no term: they are not in the table.
+// EXPR: deck strings in the coordinates, evaluated in a loop that is NOT unrolled (one inlined interpreter).
+template <int DIM, bool EXPR>
+__device__ __forceinline__ void shallowwater_point(const PointArgs<DIM> &a, Dual *F) {
+  static_assert(DIM == 2, "shallowwater is 2-D");
+  constexpr int S = 1 + DIM, NF = 6;
+  const PhysParamsDev &pp = *a.pp;
+  double fv[NF];
+  if constexpr (EXPR) {
+#pragma nounroll
+    for (int k = 0; k < NF; ++k) fv[k] = eval_func<DIM, true>(pp.f[k], a.e, a.q, a.nq, a.x);
+  } else {
+#pragma unroll
+    for (int k = 0; k < NF; ++k) fv[k] = eval_func<DIM, false>(pp.f[k], a.e, a.q, a.nq, a.x);
+  }
+  const double g = pp.p[0], bath = fv[0];
+  const Dual xi = a.U[0], Hu = a.U[S], Hv = a.U[2 * S];
+  const Dual D = xi + bath;
+  const Dual uHu = Hu * Hu / D, uHv = Hu * Hv / D, vHv = Hv * Hv / D;
+  const Dual pres = (D * D - bath * bath) * (0.5 * g);
+  F[0] = a.Ud[0] - fv[3];
+  F[1] = -Hu;
+  F[2] = -Hv;
+  F[S] = a.Ud[S] - xi * (g * fv[1]) - fv[4];
+  F[S + 1] = -(uHu + pres);
+  F[S + 2] = -uHv;
+  F[2 * S] = a.Ud[2 * S] - xi * (g * fv[2]) - fv[5];
+  F[2 * S + 1] = -uHv;
+  F[2 * S + 2] = -(vHv + pres);
+}
+
 }  // namespace mha

@@ -3,6 +3,8 @@
 #include "physics.hpp"
 #include "linearelasticity.hpp"
 #include "cdr.hpp"
+#include "shallowwater.hpp"
+#include "stokes.hpp"
 #include "helmholtz.hpp"
 #include "porous_hybrid.hpp"
 #include "porous_weak_galerkin.hpp"
@@ -596,6 +598,8 @@ std::unique_ptr<PhysicsBase> import_physics(int physics_id, int dim) {
   if (physics_id == MHA_PHYSICS_SHALLOWWATER_HYBRIDIZED) p.reset(new shallowwaterHybridized());
   if (physics_id == MHA_PHYSICS_POROUS_MIXED_HYBRIDIZED) p.reset(new porousMixedHybridized());
   if (physics_id == MHA_PHYSICS_POROUS_WEAK_GALERKIN) p.reset(new porousWeakGalerkin());
+  if (physics_id == MHA_PHYSICS_STOKES) p.reset(new stokes(dim));
+  if (physics_id == MHA_PHYSICS_SHALLOWWATER) p.reset(new shallowwater());
   MHA_REQUIRE(p != nullptr, MHA_ERR_INVALID, "unknown physics module id " << physics_id);
   p->id = physics_id;
   return p;
