@@ -47,7 +47,12 @@ __global__ __launch_bounds__(64 * kProductMaxWaves) void jacobian_diagonal_kerne
   using L = Layout<PHYS, DIM>;
   constexpr int NS = L::NS, GEO = geo_size<DIM>(), CS = coupling_size<L, DIM>();
   extern __shared__ double smem[];
-  const int NQ = vl.nq, n = vl.n_tot, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, NW = blockDim.x >> 6;
+  // wave: the same in every lane, and said so to the compiler -- the element loop is then a scalar loop.  As a per-lane
+  // value it made the element loop one with a divergent exit, and under the register pressure of the 3-D deck-string
+  // builds the copies and spills of values live across the dof-gather loop were placed in front of the exec restore
+  // behind that loop, where no lane is active (check_exec_restore.awk)
+  const int NQ = vl.nq, n = vl.n_tot, tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63,
+            NW = blockDim.x >> 6;
   double *tab = smem;
   double *s_Uh = tab + vl.tables_size + wave * (int)diag_wave_doubles(vl, GEO, CS);
   double *s_Udh = s_Uh + NQ * NS, *s_C = s_Udh + NQ * NS;

@@ -1,4 +1,5 @@
-"""The extended-precision yardstick of the HGRAD modules (thermal, navierstokes, linearelasticity): element arrays,
+"""The extended-precision yardstick of the HGRAD modules (thermal, navierstokes, linearelasticity, cdr, helmholtz, stokes,
+shallowwater and the coupled blocks navierstokes+thermal, linearelasticity+thermal, navierstokes+cdr): element arrays,
 global CRS values and residuals in numpy's 80-bit longdouble / clongdouble (eps 1.08e-19) from 1-D ingredients that mpmath
 computes at 40 digits, and beside every entry the SCALE of its own sum, so that an entry is judged by its own condition.
 
@@ -21,6 +22,15 @@ Reference lines restated here:
   * thermal::volumeResidual                  src/physics/thermal.cpp:125-163
   * navierstokes::volumeResidual, computeTau src/physics/navierstokes.cpp:82-849, :1054-1079 (uz through uy's offsets: :688)
   * linearelasticity::volumeResidual, computeStress  src/physics/linearelasticity.cpp:92-238, :985-1073
+  * stokes::volumeResidual                   src/physics/stokes.cpp:178-438 (PSPG tau h / (2 nu) in 2-D :256, h^2 / (2 nu) in
+                                             3-D :402; LSIC tested with the sum of the derivatives of q :283, :432)
+  * shallowwater::volumeResidual             src/physics/shallowwater.cpp:118-153 (gravity 9.8: :32)
+  * helmholtz::volumeResidual                src/physics/helmholtz.cpp:134-194 (vr and vi: :156-157, the two rows :175-193)
+  * cdr::volumeResidual                      src/physics/cdr.cpp:62-142
+  * navierstokes with have_energy            src/physics/navierstokes.cpp:134-141, :168-176, :471-483, :824-838 (the PSPG
+                                             buoyancy part is not divided by the density)
+  * thermal with have_nsvel, have_advection  src/physics/thermal.cpp:139-160
+  * computeStress with e_num >= 0            src/physics/linearelasticity.cpp:1001-1011, :1024-1034, :1074-1084
   * Workset::computeSolnTransientSeeded      src/tools/workset.cpp:589-623
   * Workset::getElementSize                  src/tools/workset.cpp:2666-2679
   * the scatter (-res.val(), +res.dx(col), fixed rows skipped)  src/managers/assemblyManager.cpp:4031-4145
@@ -69,6 +79,57 @@ K_ORACLE = {
     ("linearelasticity", "units small"):       25,      # measured 19.28
     ("linearelasticity", "units large"):       23,      # measured 18.38
     ("linearelasticity", "unit plane stress"): 23,      # measured 18.28
+    # the later point-engine modules: Python restatements on einsum, every one (the measurement times 1.25)
+    ("cdr",                      "unit"):               18,      # measured 14.1
+    ("cdr",                      "stretched aligned"):  26,      # measured 20.18
+    ("cdr",                      "stretched sheared"):  1400,    # measured 1045
+    ("cdr",                      "stretched warped"):   27,      # measured 21.06
+    ("cdr",                      "units small"):        19,      # measured 14.95
+    ("cdr",                      "units large"):        16,      # measured 12.66
+    ("cdr",                      "unit fields"):        21,      # measured 16.07
+    ("cdr",                      "unit arrays"):        19,      # measured 14.52
+    ("helmholtz",                "unit"):               19,      # measured 14.49
+    ("helmholtz",                "stretched aligned"):  23,      # measured 18.11
+    ("helmholtz",                "stretched sheared"):  1400,    # measured 1048
+    ("helmholtz",                "stretched warped"):   25,      # measured 19.66
+    ("helmholtz",                "units small"):        22,      # measured 16.88
+    ("helmholtz",                "units large"):        22,      # measured 17.51
+    ("helmholtz",                "unit all functions"): 15,      # measured 11.36
+    ("stokes",                   "unit"):               24,      # measured 18.79 (the worst of the four PSPG / LSIC settings)
+    ("stokes",                   "stretched aligned"):  27,      # measured 21.49
+    ("stokes",                   "stretched sheared"):  1800,    # measured 1372
+    ("stokes",                   "stretched warped"):   47,      # measured 36.93
+    ("stokes",                   "units small"):        34,      # measured 26.85
+    ("stokes",                   "units large"):        34,      # measured 26.69
+    ("shallowwater",             "unit"):               44,      # measured 35.06 (the stage-1 residual: the seeded xi_t cancels)
+    ("shallowwater",             "stretched aligned"):  65,      # measured 51.79
+    ("shallowwater",             "stretched sheared"):  1800,    # measured 1383
+    ("shallowwater",             "stretched warped"):   44,      # measured 34.69
+    ("shallowwater",             "units small"):        44,      # measured 34.67
+    ("shallowwater",             "units large"):        47,      # measured 37.2
+    ("shallowwater",             "small elevation"):    73,      # measured 57.92 (D D - b b cancels: its own round-off)
+    ("navierstokes+thermal",     "unit"):               43,      # measured 34.28
+    ("navierstokes+thermal",     "stretched aligned"):  96,      # measured 76.46
+    ("navierstokes+thermal",     "stretched sheared"):  1300,    # measured 1022
+    ("navierstokes+thermal",     "stretched warped"):   45,      # measured 35.93
+    ("navierstokes+thermal",     "units small"):        49,      # measured 38.61
+    ("navierstokes+thermal",     "units large"):        56,      # measured 44.3
+    ("navierstokes+thermal",     "unit plain"):         43,      # measured 34.28
+    ("navierstokes+thermal",     "rest"):               44,      # measured 34.84
+    ("linearelasticity+thermal", "unit"):               31,      # measured 24.16
+    ("linearelasticity+thermal", "stretched aligned"):  24,      # measured 18.75
+    ("linearelasticity+thermal", "stretched sheared"):  1800,    # measured 1394
+    ("linearelasticity+thermal", "stretched warped"):   34,      # measured 26.64
+    ("linearelasticity+thermal", "units small"):        27,      # measured 21.15
+    ("linearelasticity+thermal", "units large"):        28,      # measured 22
+    ("linearelasticity+thermal", "unit plane stress"):  30,      # measured 23.69
+    ("navierstokes+cdr",         "unit"):               24,      # measured 18.97
+    ("navierstokes+cdr",         "stretched aligned"):  36,      # measured 28.71
+    ("navierstokes+cdr",         "stretched sheared"):  1200,    # measured 889.3
+    ("navierstokes+cdr",         "stretched warped"):   42,      # measured 33.1
+    ("navierstokes+cdr",         "units small"):        34,      # measured 26.78
+    ("navierstokes+cdr",         "units large"):        57,      # measured 45.22
+    ("navierstokes+cdr",         "unit fields"):        27,      # measured 20.91
 }
 
 
@@ -217,7 +278,7 @@ class Block:
     """m: a mesh dict of tests/oracle_lib.py's layout (nodes, lids, offsets, ndof and, for several variables, orders and
     varptr; a single-variable mesh gives `order`).  Slots: variable v -> [value, d/dx, d/dy(, d/dz)] at v (1 + dim)."""
 
-    def __init__(self, m, qdeg, order=None, test_var=None):
+    def __init__(self, m, qdeg, order=None, test_var=None, test_slots=None):
         self.nodes = np.asarray(m["nodes"], dtype=np.float64)
         self.lids = np.asarray(m["lids"])
         self.E, self.n = self.lids.shape
@@ -249,6 +310,14 @@ class Block:
             for v, tv in enumerate(test_var):
                 assert self.orders[v] == self.orders[tv]
                 self.Ttest[:, self.offs[tv], :, v * self.S:(v + 1) * self.S] += T[:, self.offs[v], :, v * self.S:(v + 1) * self.S]
+        # test_slots[g] = (rv, bv): the point function gives len(test_slots) groups of 1 + dim outputs; group g multiplies
+        # basis function i of variable bv (value, gradient) and goes to row i of variable rv (helmholtz: vr and vi apart)
+        if test_slots is not None:
+            assert test_var is None
+            self.Ttest = np.zeros((self.E, self.n, self.nq, len(test_slots) * self.S), LD)
+            for g, (rv, bv) in enumerate(test_slots):
+                assert self.orders[rv] == self.orders[bv]
+                self.Ttest[:, self.offs[rv], :, g * self.S:(g + 1) * self.S] += T[:, self.offs[bv], :, bv * self.S:(bv + 1) * self.S]
 
     # -- its own check of the dof ordering -------------------------------------------------------------------------------
     def check_ordering(self):
@@ -307,15 +376,44 @@ class Block:
 
 
 # ---- the modules as point functions F(U, Udot, x, params) ----------------------------------------------------------------
-def func_value(spec, x):
-    """A function of the deck at the points x [E][q][dim]: a number or ("sinprod", amp, freq)."""
+def func_value(spec, x, env=None):
+    """A function of the deck at the points x [E][q][dim]: a number, ("sinprod", amp, freq), ("array", a) -- per-point
+    data [E][q], as the device takes it from a tensor -- or (callable, deck text): the device and the float64 oracle get
+    the text, the yardstick calls the callable with env(), the slot values by their deck names ("c", "c_t",
+    "grad(c)[x]", "ux", "x", ...), so that a string that reads the fields is differentiated by the complex step."""
     if isinstance(spec, (int, float)):
         return LD(spec)
+    if isinstance(spec, mpmath.mpf):                            # the point functions on mpf (tests/test_highprec.py)
+        return spec
+    if callable(spec[0]):
+        return spec[0](env())
+    if spec[0] == "array":
+        return np.asarray(spec[1]).astype(LD)
     assert spec[0] == "sinprod"
     v = LD(spec[1])
     for d in range(x.shape[2]):
         v = v * np.sin(LD(spec[2][d]) * x[..., d])
     return v
+
+
+def deck_function(spec):
+    """What the device and the float64 oracle are given for a function: the text of a (callable, text) pair, else spec."""
+    return spec[1] if isinstance(spec, tuple) and callable(spec[0]) else spec
+
+
+def slot_env(names, U, Ud, x):
+    """The slot values by the names a deck string reads them under (Workset::getSolutionField) and the coordinates."""
+    dim = x.shape[2]
+    S = 1 + dim
+
+    def env():
+        f = {c: x[..., d] for d, c in enumerate("xyz"[:dim])}
+        for v, nm in enumerate(names):
+            f[nm], f[nm + "_t"] = U[v * S], Ud[v * S]
+            for d, c in enumerate("xyz"[:dim]):
+                f["grad(%s)[%s]" % (nm, c)] = U[v * S + 1 + d]
+        return f
+    return env
 
 
 def thermal_point(U, Ud, x, P):
@@ -333,12 +431,21 @@ def thermal_point(U, Ud, x, P):
     return F
 
 
+def _num(v):
+    """A number of the deck as longdouble; an mpf stays (the point functions on mpf, tests/test_highprec.py)."""
+    return v if isinstance(v, mpmath.mpf) else LD(v)
+
+
 def compute_tau(visc, vel, h, dt, transient):
     """navierstokes.cpp:1054-1079; the branch nvel > 1e-12 is taken on the real part."""
     C1, C2, C3 = LD(4), LD(2), LD(2) if transient else LD(0)
     nvel = vel[0] * vel[0]
     for v in vel[1:]:
         nvel = nvel + v * v
+    if isinstance(nvel, mpmath.mpf):                            # on mpf: the same branch and formula, one point
+        nvel = mpmath.sqrt(nvel) if nvel > 1e-12 else nvel
+        tau = (4 * visc / h / h) * (4 * visc / h / h) + (2 * nvel / h) * (2 * nvel / h) + (int(C3) / dt) * (int(C3) / dt)
+        return 1 / mpmath.sqrt(tau)
     nvel = np.where(np.real(nvel) > 1e-12, np.sqrt(np.where(np.real(nvel) > 1e-12, nvel, 1)), nvel)
     tau = (C1 * visc / h / h) * (C1 * visc / h / h) + (C2 * nvel / h) * (C2 * nvel / h) + (C3 / dt) * (C3 / dt)
     return 1 / np.sqrt(tau)
@@ -355,10 +462,15 @@ def navierstokes_point(U, Ud, x, P):
     vel = [U[v * S] for v in vn]
     pr = U[pn * S]
     supg, pspg = bool(P.get("useSUPG")), bool(P.get("usePSPG"))
-    tau = compute_tau(visc, vel, P["h"], LD(P["dt"]), bool(P["transient"])) if supg or pspg else None
+    tau = compute_tau(visc, vel, P["h"], _num(P["dt"]), bool(P["transient"])) if supg or pspg else None
     F = [None] * ((dim + 1) * S)
     divu = 0
     strong = []
+    # have_energy (the coupled block navierstokes+thermal): P["energy"] = (the variable number of e, beta, T_ambient)
+    buoy = None
+    if P.get("energy") is not None:
+        ev, beta, T0 = P["energy"]
+        buoy = [dens * _num(beta) * (U[ev * S] - _num(T0)) * src[i] for i in range(dim)]   # :141, :176, :480
     for i, v in enumerate(vn):
         b = v * S
         conv = sum(vel[d] * U[b + 1 + d] for d in range(dim))
@@ -371,9 +483,16 @@ def navierstokes_point(U, Ud, x, P):
         if supg:
             for d in range(dim):
                 F[b + 1 + d] = F[b + 1 + d] + tau * strong[i] * vel[d]          # :555-559
+        if buoy is not None:
+            F[b] = F[b] + buoy[i]                                                # :134-147
+            if supg:
+                for d in range(dim):
+                    F[b + 1 + d] = F[b + 1 + d] + tau * buoy[i] * vel[d]        # :168-185
     F[pn * S] = divu                                                            # :782-784
     for d in range(dim):
         F[pn * S + 1 + d] = strong[d] * tau / dens if pspg else 0 * pr          # :813-820
+        if pspg and buoy is not None:
+            F[pn * S + 1 + d] = F[pn * S + 1 + d] + buoy[d] * tau                # :471-488, :824-845: not over the density
     return F
 
 
@@ -398,7 +517,150 @@ def linearelasticity_point(U, Ud, x, P):
     return F
 
 
-POINT = {"thermal": thermal_point, "navierstokes": navierstokes_point, "linearelasticity": linearelasticity_point}
+def stokes_point(U, Ud, x, P):
+    """stokes.cpp:178-438, variables ux, pr, uy[, uz]; params: source ux / uy / uz, viscosity, usePSPG, useLSIC, h.  No
+    time term; "source pr" is read by no term; the uz rows go through their own offsets."""
+    dim = x.shape[2]
+    S = 1 + dim
+    vn, pn = [0, 2, 3][:dim], 1
+    visc = func_value(P["viscosity"], x)
+    src = [func_value(P["source u" + c], x) for c in "xyz"[:dim]]
+    pr, h = U[pn * S], P["h"]
+    F = [None] * ((dim + 1) * S)
+    divu = 0
+    for i, v in enumerate(vn):
+        b = v * S
+        F[b] = -src[i] + 0 * pr                                                  # g of :197, :218, :364
+        for d in range(dim):
+            F[b + 1 + d] = visc * U[b + 1 + d] - (pr if d == i else 0)           # Fx, Fy, Fz of :193-195, :312-316
+        divu = divu + U[b + 1 + i]
+    F[pn * S] = divu                                                            # :236, :382
+    for d in range(dim):
+        F[pn * S + 1 + d] = 0 * pr
+    if P.get("usePSPG"):
+        tau = (h if dim == 2 else h * h) / (2.0 * visc)                          # :256 and :402
+        for d in range(dim):
+            F[pn * S + 1 + d] = F[pn * S + 1 + d] + (U[pn * S + 1 + d] + src[d]) * tau      # :257-262, :403-410
+    if P.get("useLSIC"):
+        tau = h * h / (2.0 * visc)                                               # :279, :428
+        for d in range(dim):
+            F[pn * S + 1 + d] = F[pn * S + 1 + d] + tau * divu                   # S (q_x + q_y [+ q_z]) of :283, :432
+    return F
+
+
+def shallowwater_point(U, Ud, x, P):
+    """shallowwater.cpp:118-153, variables H (holding the surface elevation xi), Hu, Hv; params: bathymetry, bathymetry_x,
+    bathymetry_y, source H / Hu / Hv, gravity."""
+    S = 3
+    fv = lambda k: func_value(P[k], x)
+    bath, g = fv("bathymetry"), P.get("gravity", 9.8)                            # :32
+    xi, Hu, Hv = U[0], U[S], U[2 * S]
+    F = [None] * (3 * S)
+    F[0], F[1], F[2] = Ud[0] - fv("source H"), -Hu, -Hv                          # :124-126
+    D = xi + bath                                                                # :131
+    uHu, uHv, vHv = Hu * Hu / D, Hu * Hv / D, Hv * Hv / D                        # :132-134
+    pres = 0.5 * g * (D * D - bath * bath)                                       # :137, :145
+    F[S] = Ud[S] - g * xi * fv("bathymetry_x") - fv("source Hu")                 # :136
+    F[S + 1], F[S + 2] = -(uHu + pres), -uHv                                     # :137-138
+    F[2 * S] = Ud[2 * S] - g * xi * fv("bathymetry_y") - fv("source Hv")         # :143
+    F[2 * S + 1], F[2 * S + 2] = -uHv, -(vHv + pres)                             # :144-145
+    return F
+
+
+HELMHOLTZ_TEST_SLOTS = [(0, 0), (0, 1), (1, 0), (1, 1)]          # (the variable whose rows, the variable whose basis)
+
+
+def helmholtz_point(U, Ud, x, P):
+    """helmholtz.cpp:134-194, the non-fractional branch, variables ureal, uimag, with vr = ureal's basis function i and
+    vi = uimag's basis function i kept apart: four groups of test slots (Block(test_slots=HELMHOLTZ_TEST_SLOTS)) -- what
+    multiplies (vr, grad vr) and (vi, grad vi) in the ureal row :175-182, then the same of the uimag row :186-193.
+    params: c2r_x .. c2i_z, omega2r, omega2i, source_r, source_i.  No time term."""
+    dim = x.shape[2]
+    S = 1 + dim
+    fv = lambda k: func_value(P[k], x)
+    o2r, o2i, sr, si = fv("omega2r"), fv("omega2i"), fv("source_r"), fv("source_i")
+    ur, ui = U[0], U[S]
+    F = [None] * (4 * S)
+    F[0] = -o2r * ur + o2i * ui - sr                                             # the ureal row, vr
+    F[S] = -o2r * ui - o2i * ur - si                                             # the ureal row, vi
+    F[2 * S] = -o2r * ui - o2i * ur - si                                         # the uimag row, vr
+    F[3 * S] = o2r * ur - o2i * ui + sr                                          # the uimag row, vi
+    for d, c in enumerate("xyz"[:dim]):
+        c2r, c2i = fv("c2r_" + c), fv("c2i_" + c)
+        dur, dui = U[1 + d], U[S + 1 + d]
+        F[1 + d] = c2r * dur - c2i * dui
+        F[S + 1 + d] = c2r * dui + c2i * dur
+        F[2 * S + 1 + d] = c2r * dui + c2i * dur
+        F[3 * S + 1 + d] = -c2r * dur + c2i * dui
+    return F
+
+
+def cdr_row(U, Ud, x, P, names):
+    """cdr.cpp:112-140 on c, the LAST variable of names: [f, Fx, Fy(, Fz)].  params: source, diffusion, specific heat,
+    density, reaction, xvel, yvel, zvel; each may read the fields ((callable, text), func_value)."""
+    dim = x.shape[2]
+    S = 1 + dim
+    b = (len(names) - 1) * S
+    env = slot_env(names, U, Ud, x)
+    fv = lambda k: func_value(P[k], x, env)
+    f = Ud[b] + fv("reaction") - fv("source")                                    # no rho cp on the time derivative
+    for d, c in enumerate("xyz"[:dim]):
+        f = f + fv(c + "vel") * U[b + 1 + d]
+    kd = 1.0 / (fv("density") * fv("specific heat")) * fv("diffusion")
+    return [f] + [kd * U[b + 1 + d] for d in range(dim)]
+
+
+def cdr_point(U, Ud, x, P):
+    return cdr_row(U, Ud, x, P, ["c"])
+
+
+def navierstokes_cdr_point(U, Ud, x, P):
+    """navierstokes' rows as navierstokes_point gives them, then cdr's on c; "density" is one function for both."""
+    dim = x.shape[2]
+    return navierstokes_point(U, Ud, x, P) + cdr_row(U, Ud, x, P, ["ux", "pr", "uy", "uz"][:dim + 1] + ["c"])
+
+
+def navierstokes_thermal_point(U, Ud, x, P):
+    """navierstokes with have_energy, then thermal.cpp:125-163 with have_nsvel on e, the last variable; params besides
+    navierstokes': thermal source, thermal diffusion, specific heat, beta, T_ambient, include advection with bx, by, bz."""
+    dim = x.shape[2]
+    S = 1 + dim
+    vn, b = [0, 2, 3][:dim], (dim + 1) * S
+    fv = lambda k: func_value(P[k], x)
+    F = navierstokes_point(U, Ud, x, dict(P, energy=(dim + 1, P["beta"], P["T_ambient"])))
+    f = fv("density") * fv("specific heat") * Ud[b] - fv("thermal source")       # :131
+    for d in range(dim):
+        f = f + U[vn[d] * S] * U[b + 1 + d]                                       # :139-149
+        if P.get("include advection"):
+            f = f + fv("b" + "xyz"[d]) * U[b + 1 + d]                             # :150-160
+    return F + [f] + [fv("thermal diffusion") * U[b + 1 + d] for d in range(dim)]
+
+
+def linearelasticity_thermal_point(U, Ud, x, P):
+    """linearelasticity with e_num >= 0: every normal stress gets -alpha_T (e - T_ambient) c, c = 3 lambda + 2 mu, or 5 mu
+    under incplanestress in 2-D (linearelasticity.cpp:1007-1008, :1030-1031, :1080-1082); then thermal.cpp:125-163 without
+    have_nsvel on e, the last variable."""
+    dim = x.shape[2]
+    S = 1 + dim
+    b = dim * S
+    fv = lambda k: func_value(P[k], x)
+    lam, mu = fv("lambda"), fv("mu")
+    F = linearelasticity_point(U, Ud, x, P)
+    c = 5 * mu if dim == 2 and P.get("incplanestress") else 3 * lam + 2 * mu
+    th = _num(P["alpha_T"]) * (U[b] - _num(P["T_ambient"])) * c
+    for i in range(dim):
+        F[i * S + 1 + i] = F[i * S + 1 + i] - th
+    f = fv("density") * fv("specific heat") * Ud[b] - fv("thermal source")
+    if P.get("include advection"):
+        for d in range(dim):
+            f = f + fv("b" + "xyz"[d]) * U[b + 1 + d]
+    return F + [f] + [fv("thermal diffusion") * U[b + 1 + d] for d in range(dim)]
+
+
+POINT = {"thermal": thermal_point, "navierstokes": navierstokes_point, "linearelasticity": linearelasticity_point,
+         "stokes": stokes_point, "shallowwater": shallowwater_point, "helmholtz": helmholtz_point, "cdr": cdr_point,
+         "navierstokes+cdr": navierstokes_cdr_point, "navierstokes+thermal": navierstokes_thermal_point,
+         "linearelasticity+thermal": linearelasticity_thermal_point}
 
 
 def _stack(F, like):
@@ -406,11 +668,11 @@ def _stack(F, like):
 
 
 def point_derivative(point, U, Ud, x, P):
-    """F [K][E][q], dF/dU and dF/dUdot [K out][K in][E][q] by the complex step Im F(U + i h e_k) / h, h = 1e-30."""
+    """F [K out][E][q], dF/dU and dF/dUdot [K out][K in][E][q] by the complex step Im F(U + i h e_k) / h, h = 1e-30."""
     K = U.shape[0]
     Uc, Udc = U.astype(CLD), Ud.astype(CLD)
     F = np.real(_stack(point(Uc, Udc, x, P), Uc)).astype(LD)
-    CU, CT = np.zeros((K, K) + U.shape[1:], LD), np.zeros((K, K) + U.shape[1:], LD)
+    CU, CT = np.zeros((F.shape[0], K) + U.shape[1:], LD), np.zeros((F.shape[0], K) + U.shape[1:], LD)
     S = 1 + x.shape[2]
     for k in range(K):
         Up = Uc.copy()
@@ -535,19 +797,81 @@ SHAPES = {  # module -> (name, dim, ncell, orders)
                      ("3-D Q2/Q1", 3, (2, 1, 1), (2, 1, 2, 2))],
     "linearelasticity": [("2-D Q1", 2, (3, 2), (1, 1)), ("2-D Q2", 2, (3, 2), (2, 2)), ("3-D Q1", 3, (2, 2, 2), (1, 1, 1)),
                          ("3-D Q2", 3, (2, 1, 1), (2, 2, 2))],
+    # the later point-engine modules: the shapes of their own GPU tests, the smallest that reach every instantiation family
+    "cdr": [("2-D Q1", 2, (3, 2), (1,)), ("2-D Q2", 2, (3, 2), (2,)), ("3-D Q1", 3, (2, 3, 2), (1,)), ("3-D Q2", 3, (2, 2, 2), (2,))],
+    "helmholtz": [("2-D Q1", 2, (3, 3), (1, 1)), ("2-D Q2", 2, (2, 2), (2, 2)), ("3-D Q1", 3, (2, 2, 2), (1, 1)),
+                  ("3-D Q2", 3, (2, 2, 1), (2, 2))],
+    "stokes": [("2-D Q1/Q1", 2, (3, 3), (1, 1, 1)), ("2-D Q2/Q1", 2, (3, 3), (2, 1, 2)), ("3-D Q1/Q1", 3, (2, 2, 2), (1, 1, 1, 1)),
+               ("3-D Q2/Q1", 3, (2, 2, 2), (2, 1, 2, 2))],
+    "shallowwater": [("2-D Q1", 2, (3, 3), (1, 1, 1)), ("2-D Q2", 2, (3, 3), (2, 2, 2))],
+    "navierstokes+thermal": [("2-D Q2/Q1/Q2", 2, (3, 2), (2, 1, 2, 2)), ("3-D Q1", 3, (2, 2, 2), (1, 1, 1, 1, 1))],
+    "linearelasticity+thermal": [("2-D Q1/Q1", 2, (4, 3), (1, 1, 1)), ("2-D Q2/Q1", 2, (4, 3), (2, 2, 1)),
+                                 ("3-D Q2/Q1", 3, (2, 2, 2), (2, 2, 2, 1))],
+    "navierstokes+cdr": [("2-D Q1", 2, (3, 2), (1, 1, 1, 1)), ("2-D Q2/Q1/Q2", 2, (3, 2), (2, 1, 2, 2)),
+                         ("3-D Q1", 3, (2, 2, 2), (1, 1, 1, 1, 1))],
 }
 FAMILIES = ["unit", "stretched aligned", "stretched sheared", "stretched warped", "units small", "units large"]
 # the terms of thermal that only the point engine has, on the unit family's inputs: (b . grad e, v) and kappa = 1 + e*e
 THERMAL_ONLY = ["unit advection", "unit nonlinear"]
+# the branches that only one of the later modules has, on the unit family's geometry
+MODULE_ONLY = {
+    "thermal": THERMAL_ONLY, "navierstokes": ["rest"], "linearelasticity": ["unit plane stress"],
+    "cdr": ["unit fields", "unit arrays"],                 # deck strings that read c, c_t, grad(c); every function per point
+    "navierstokes+cdr": ["unit fields"],                   # ... and ux
+    "helmholtz": ["unit all functions"],                   # the ten volume functions non-zero, different in every direction
+    "navierstokes+thermal": ["unit plain", "rest"],        # no stabilisation, b . grad e; computeTau at |u| = 0
+    "linearelasticity+thermal": ["unit plane stress"],
+    "shallowwater": ["small elevation"],                   # |xi| ~ 1e-3 b: D D - b b cancels
+}
+# stokes: the four (usePSPG, useLSIC) settings under ONE family key (the worst d over the four)
+VARIANTS = {"stokes": [dict(usePSPG=0, useLSIC=0), dict(usePSPG=1, useLSIC=0), dict(usePSPG=0, useLSIC=1), dict(usePSPG=1, useLSIC=1)]}
+# the deck's names per module: the functions the yardstick reads, the physics parameters
+NS_FUNCS = ["source ux", "source uy", "source uz", "viscosity", "density"]
+LE_FUNCS = ["lambda", "mu", "source dx", "source dy", "source dz"]
+MODULE_FUNCS = {
+    "navierstokes": NS_FUNCS, "linearelasticity": LE_FUNCS,
+    "stokes": ["source ux", "source uy", "source uz", "viscosity"],
+    "shallowwater": ["bathymetry", "bathymetry_x", "bathymetry_y", "source H", "source Hu", "source Hv"],
+    "helmholtz": ["c2r_x", "c2i_x", "c2r_y", "c2i_y", "c2r_z", "c2i_z", "omega2r", "omega2i", "source_r", "source_i"],
+    "cdr": ["source", "diffusion", "specific heat", "density", "reaction", "xvel", "yvel", "zvel"],
+    "navierstokes+cdr": NS_FUNCS + ["source", "diffusion", "specific heat", "reaction", "xvel", "yvel", "zvel"],
+    "navierstokes+thermal": NS_FUNCS + ["thermal source", "thermal diffusion", "specific heat", "bx", "by", "bz"],
+    "linearelasticity+thermal": LE_FUNCS + ["thermal source", "thermal diffusion", "specific heat", "density", "bx", "by", "bz"],
+}
+MODULE_PARAMS = {
+    "navierstokes": ["useSUPG", "usePSPG", "fix_uz_offsets"], "linearelasticity": ["incplanestress"],
+    "stokes": ["usePSPG", "useLSIC"], "shallowwater": [], "helmholtz": [], "cdr": [],
+    "navierstokes+cdr": ["useSUPG", "usePSPG", "fix_uz_offsets"],
+    "navierstokes+thermal": ["useSUPG", "usePSPG", "fix_uz_offsets", "beta", "T_ambient", "include advection"],
+    "linearelasticity+thermal": ["incplanestress", "alpha_T", "T_ambient", "include advection"],
+}
 
 
 def families(module):
-    return FAMILIES + {"thermal": THERMAL_ONLY, "navierstokes": ["rest"], "linearelasticity": ["unit plane stress"]}.get(module, [])
+    return FAMILIES + MODULE_ONLY.get(module, [])
 
 
 def transients(module, family):
     """steady and stage 1; the nonlinear diffusion's oracle (oracle_lib.assemble_thermal_fields) is steady only."""
     return (False,) if family == "unit nonlinear" else (False, True)
+
+
+def case_list(module, family):
+    """(shape, transient, variant) of every case of a (module, family) key."""
+    return [(shape, tr, v) for shape in SHAPES[module] for tr in transients(module, family)
+            for v in range(len(VARIANTS.get(module, [None])))]
+
+
+def deck(c):
+    """(functions, physics parameters) of a case as the device and the float64 restatements are given them: names of the
+    third direction left out in 2-D, deck text for (callable, text), the named helper strings, and the functions that the
+    reference registers and no term reads."""
+    P, z = c["P"], c["dim"] == 2
+    funcs = {k: deck_function(P[k]) for k in MODULE_FUNCS[c["module"]]
+             if k in P and not (z and (k.endswith("z") or k == "zvel"))}
+    funcs.update(P.get("unread", {}))
+    funcs.update(P.get("helpers", {}))
+    return funcs, {k: P[k] for k in MODULE_PARAMS[c["module"]] if k in P}
 
 
 def sinprod_text(spec, dim):
@@ -614,13 +938,134 @@ def case_data(module, family, dim, ndof, dof_var, transient, seed=97):
     return u, tr, P
 
 
+LATER = ("cdr", "helmholtz", "stokes", "shallowwater", "navierstokes+thermal", "linearelasticity+thermal", "navierstokes+cdr")
+
+
+def later_case_data(module, family, dim, ndof, dof_var, transient, variant, nelem, nq, seed=131):
+    """case_data of the later point-engine modules.  Every coefficient, source and dt follows the units: with lengths L,
+    coefficients coef and amplitudes amp the terms of each equation keep their unit-family balance, so no term drops
+    below the others' round-off."""
+    rng = np.random.default_rng(seed)
+    L = {"units small": 1e-3, "units large": 1e3}.get(family, 1.0)
+    coef = {"units small": 1e6, "units large": 1e-6}.get(family, 1.0)
+    amp = 1e3 if family.startswith("units") else 1.0
+    dof_var = np.asarray(dof_var)
+    u = amp * rng.uniform(-1, 1, ndof)
+    # the time scales: diffusive L^2 / kappa, advective L / |u|, the gravity wave's L (shallowwater; g is not scaled)
+    diffusive, advective = L * L / coef, L / amp
+    dt = 0.05 * {"cdr": diffusive, "linearelasticity+thermal": diffusive, "shallowwater": L, "helmholtz": L}.get(module, advective)
+    tr = None
+    if transient:
+        tr = dict(TABLEAU, dt=dt, u_prev=amp * rng.uniform(-1, 1, (ndof, 2)), u_stage=amp * rng.uniform(-1, 1, (ndof, 2)))
+    fr = [f / L for f in (1.3, 0.7, 2.1)[:dim]]
+    fr2 = [f / L for f in (0.9, 1.6, 1.1)[:dim]]
+    per_point = lambda lo, hi: ("array", rng.uniform(lo, hi, (nelem, nq)))
+    ns = lambda: {"source ux": 0.3 * amp * amp / L, "source uy": ("sinprod", 1.0 * amp * amp / L, fr), "source uz": -0.2 * amp * amp / L,
+                  "viscosity": 0.05 * coef, "density": 1.3, "useSUPG": 1, "usePSPG": 1, "fix_uz_offsets": 0,
+                  "unread": {"source pr": 5.0}}
+
+    def at_rest():                                              # the other side of nvel > 1e-12: every velocity dof 0
+        for a in (u,) + ((tr["u_prev"], tr["u_stage"]) if tr else ()):
+            a[(dof_var != 1) & (dof_var != dim + 1)] = 0.0
+
+    if module == "stokes":
+        f = coef * amp / (L * L)                                # the viscous force nu u / L^2
+        P = {"source ux": 0.3 * f, "source uy": ("sinprod", 1.0 * f, fr), "source uz": -0.2 * f, "viscosity": 0.7 * coef,
+             "unread": {"source pr": 5.0}}
+        P.update(VARIANTS["stokes"][variant])
+    elif module == "shallowwater":
+        xi = dof_var == 0
+        small = 1e-3 if family == "small elevation" else 1.0    # |xi| ~ 1e-3 b, of both signs; else xi in [0.5, 1.5] amp
+        sign = rng.choice([-1.0, 1.0], int(xi.sum())) if family == "small elevation" else 1.0
+        u[xi] = small * amp * sign * rng.uniform(0.5, 1.5, int(xi.sum()))
+        if tr is not None:                                      # every xi array the same draw plus a small one of its own:
+            for k in ("u_prev", "u_stage"):                     # the seeded depth stays positive
+                tr[k][xi] = u[xi][:, None] + small * amp * rng.uniform(-0.05, 0.05, tr[k][xi].shape)
+        # (slopes of the order of b / L: g xi b_x keeps a share of its entries beside the pressure flux that the bound sees)
+        P = {"bathymetry": ("array", amp * rng.uniform(0.5, 1.5, (nelem, nq))), "bathymetry_x": 0.5 * amp / L,
+             "bathymetry_y": ("sinprod", -0.8 * amp / L, fr), "source H": 0.2 * amp / L, "source Hu": ("sinprod", 0.4 * amp * amp / L, fr2),
+             "source Hv": -0.1 * amp * amp / L, "unread": {"viscosity": 3.0, "Coriolis": 2.0}}
+    elif module == "helmholtz":
+        k2, s = coef / (L * L), amp * coef / (L * L)
+        P = {"omega2r": 2.1 * k2, "omega2i": 0.3 * k2, "source_r": ("sinprod", 2.0 * s, fr), "source_i": 0.4 * s}
+        P.update({"c2r_" + c: 1.3 * coef for c in "xyz"}, **{"c2i_" + c: 0.4 * coef for c in "xyz"})
+        if family == "unit all functions":
+            P.update({"c2r_x": 1.3, "c2r_y": 0.8, "c2r_z": 1.9, "c2i_x": 0.4, "c2i_y": -0.6, "c2i_z": 0.25,
+                      "omega2r": ("sinprod", 2.1, fr2), "omega2i": per_point(0.2, 0.5), "source_i": ("sinprod", -1.5, fr2)})
+    elif module == "cdr":
+        k2 = coef / (L * L)
+        P = {"source": ("sinprod", 2.0 * amp * k2, fr), "diffusion": 0.9 * coef, "specific heat": 1.4, "density": 1.3,
+             "reaction": 0.6 * amp * k2, "xvel": 0.7 * coef / L, "yvel": -1.1 * coef / L, "zvel": 0.4 * coef / L,
+             "unread": {"SUPG tau": 3.0}}
+        if family == "unit arrays":
+            P.update({"source": per_point(-2, 2), "diffusion": per_point(0.5, 1.5), "specific heat": per_point(1, 2),
+                      "density": per_point(1, 2), "reaction": per_point(-1, 1), "xvel": per_point(-1, 1),
+                      "yvel": per_point(-1, 1), "zvel": per_point(-1, 1)})
+    elif module == "navierstokes+cdr":
+        P = ns()
+        P.update({"source": ("sinprod", 2.0 * amp * amp / L, fr2), "diffusion": 0.9 * coef, "specific heat": 1.4,
+                  "reaction": 0.6 * amp * amp / L, "xvel": 0.7 * amp, "yvel": -1.1 * amp, "zvel": 0.4 * amp})
+    elif module == "navierstokes+thermal":
+        P = ns()
+        P.update({"thermal source": ("sinprod", 3.0 * amp * amp / L, fr2), "thermal diffusion": 1.7 * coef, "specific heat": 1.4,
+                  "beta": 0.7 / amp, "T_ambient": 0.3 * amp, "include advection": 0})
+        if family == "unit plain":
+            P.update({"useSUPG": 0, "usePSPG": 0, "include advection": 1, "bx": 0.8, "by": -0.5, "bz": 0.3})
+        if family == "rest":
+            P["fix_uz_offsets"] = 1
+            at_rest()
+    else:
+        assert module == "linearelasticity+thermal"
+        f, k2 = coef * amp / (L * L), amp * coef / (L * L)
+        P = {"lambda": 1.1 * coef, "mu": 0.6 * coef, "source dx": 0.3 * f, "source dy": ("sinprod", 1.0 * f, fr), "source dz": -0.2 * f,
+             "thermal source": ("sinprod", 3.0 * k2, fr2), "thermal diffusion": 1.7 * coef, "specific heat": 1.4, "density": 1.3,
+             "incplanestress": 1 if family == "unit plane stress" else 0, "alpha_T": 0.35 / L, "T_ambient": 0.3 * amp,
+             "include advection": 0}
+    if family == "unit fields":
+        # deck strings that read the fields, each with its callable twin on the slot values; powers written as products
+        P["helpers"] = {"kappa0": "1+0.1*x"}
+        P["reaction"] = (lambda f: 0.5 * f["c"] * f["c"] + 0.1 * f["grad(c)[x]"] * f["grad(c)[x]"], "0.5*c*c + 0.1*grad(c)[x]^2")
+        P["diffusion"] = (lambda f: (1 + 0.1 * f["x"]) + f["c"] * f["c"], "kappa0+c*c")
+        P["xvel"] = (lambda f: f["ux"], "ux") if module == "navierstokes+cdr" else (lambda f: f["c"], "c")
+        if transient:
+            P["yvel"] = (lambda f: 0.3 * f["c_t"], "0.3*c_t")
+    return u, tr, P
+
+
+def fixed_rows(module, m):
+    """The strong rows, 10 - 30 % of all: the left side without its top edge (a whole side of a mesh two cells wide is a
+    third of a Q1 variable's rows), never the pressure; shallowwater after its drop test: Hu on the left and right sides, Hv
+    on the bottom."""
+    side, var = m["side_mask"], m["dof_var"]
+    if module == "shallowwater":
+        return (((var == 1) & ((side & 0b0011) != 0)) | ((var == 2) & ((side & 0b0100) != 0))).astype(np.uint8)
+    pinned = (side & 0b1001) == 0b0001
+    if module in ("stokes", "navierstokes+thermal", "navierstokes+cdr"):
+        pinned = pinned & (var != 1)
+    return pinned.astype(np.uint8)
+
+
+def in_point_order(meshlib, blk, qdeg, P):
+    """P with every ("array", a) taken from the ABI's order of the integration points (meshlib's) to the yardstick's:
+    an integer map, found by matching the points of the first element."""
+    if not any(isinstance(v, tuple) and v[0] == "array" for v in P.values()):
+        return P
+    ip = meshlib.physical_basis_var(blk.dim, 0, 1, qdeg, blk.nodes[:1])["ip"][0]
+    x = blk.x[0].astype(np.float64)
+    dist = np.abs(x[:, None, :] - ip[None, :, :]).max(axis=2)
+    perm = dist.argmin(axis=1)
+    size = np.ptp(blk.nodes[0], axis=0).max()
+    assert sorted(perm) == list(range(blk.nq)) and dist[np.arange(blk.nq), perm].max() < 1e-12 * size
+    return {k: ("array", np.asarray(v[1])[:, perm]) if isinstance(v, tuple) and v[0] == "array" else v for k, v in P.items()}
+
+
 _CASES = {}
 
 
-def build_case(meshlib, module, shape, family, transient):
+def build_case(meshlib, module, shape, family, transient, variant=0):
     """One case, cached: mesh (meshlib: tests/oracle_lib.py, used for the structured mesh and its integer maps only),
     data, the yardstick's element arrays `el` and global arrays `g`."""
-    key = (module, shape, family, transient)
+    key = (module, shape, family, transient, variant)
     if key in _CASES:
         return _CASES[key]
     name, dim, ncell, orders = shape
@@ -632,15 +1077,26 @@ def build_case(meshlib, module, shape, family, transient):
         m = meshlib.mesh_multi(dim, ncell, [0] * len(orders), list(orders))
         pinned = (m["side_mask"] & 0b1100) != 0                               # strong Dirichlet rows on two sides
         fixed = (pinned & (m["dof_var"] != 1) if module == "navierstokes" else pinned).astype(np.uint8)
-    m["verts"] = map_vertices(m["verts"], family)
+        if module in LATER:
+            fixed = fixed_rows(module, m)
+    m["verts"] = map_vertices(m["verts"], family if family in FAMILIES or module not in LATER else "unit")
     m["nodes"] = np.ascontiguousarray(m["verts"][m["cell2vert"]])
     qdeg = 2 * orders[0]
-    u, tr, P = case_data(module, family, dim, m["ndof"], m["dof_var"], transient)
-    quirk = module == "navierstokes" and dim == 3 and not P["fix_uz_offsets"]
-    blk = Block(m, qdeg, order=orders[0] if module == "thermal" else None, test_var=[0, 1, 2, 2] if quirk else None)
+    if module in LATER:
+        u, tr, P = later_case_data(module, family, dim, m["ndof"], m["dof_var"], transient, variant, m["nelem"],
+                                   gauss_npts(qdeg) ** dim)
+    else:
+        u, tr, P = case_data(module, family, dim, m["ndof"], m["dof_var"], transient)
+    # the uz rows through uy's offsets (navierstokes.cpp:688), in the coupled blocks too
+    quirk = module.startswith("navierstokes") and dim == 3 and not P["fix_uz_offsets"]
+    blk = Block(m, qdeg, order=orders[0] if module == "thermal" else None,
+                test_var=([0, 1, 2, 2] + list(range(4, len(orders)))) if quirk else None,
+                test_slots=HELMHOLTZ_TEST_SLOTS if module == "helmholtz" else None)
     blk.check_ordering()
-    el = element_arrays(blk, module, P, u, tr)
+    el = element_arrays(blk, module, in_point_order(meshlib, blk, qdeg, P), u, tr)
     c = dict(module=module, shape=shape, family=family, m=m, dim=dim, orders=orders, qdeg=qdeg, u=u, tr=tr, P=P, fixed=fixed,
-             blk=blk, el=el, g=assemble(blk, el, fixed))
+             blk=blk, el=el, g=assemble(blk, el, fixed), variant=variant,
+             tag="%s %s" % (name, "stage 1" if transient else "steady") +
+                 ("" if module not in VARIANTS else " " + " ".join("%s=%d" % kv for kv in VARIANTS[module][variant].items())))
     _CASES[key] = c
     return c

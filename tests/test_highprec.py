@@ -123,6 +123,87 @@ def test_complex_step_matches_mpmath_diff_of_the_navierstokes_point_function(dim
                 assert abs(H._ld(mpmath.diff(g, 0)) - CT[k, l, 0, 0]) < 1e-17 * max(1.0, float(abs(mpmath.diff(g, 0)))), (k, l)
 
 
+def _fields_of_c(module):
+    """cdr's deck strings that read the fields, as callables on the slot values (highprec_ref.later_case_data)."""
+    return {"reaction": (lambda f: 0.5 * f["c"] * f["c"] + 0.1 * f["grad(c)[x]"] * f["grad(c)[x]"], "0.5*c*c + 0.1*grad(c)[x]^2"),
+            "diffusion": (lambda f: (1 + 0.1 * f["x"]) + f["c"] * f["c"], "kappa0+c*c"),
+            "xvel": (lambda f: f["ux"], "ux") if module == "navierstokes+cdr" else (lambda f: f["c"], "c"),
+            "yvel": (lambda f: 0.3 * f["c_t"], "0.3*c_t")}
+
+
+NS_NUMBERS = {"source ux": 0.3, "source uy": 0.7, "source uz": -0.2, "viscosity": 0.05, "density": 1.3, "useSUPG": 1, "usePSPG": 1,
+              "dt": 0.05, "transient": True}
+POINT_PARAMS = {     # numbers only (they go to mpf as they stand); every switch on
+    "stokes": {"source ux": 0.3, "source uy": 0.7, "source uz": -0.2, "viscosity": 0.7, "usePSPG": 1, "useLSIC": 1},
+    "shallowwater": {"bathymetry": 1.1, "bathymetry_x": 0.3, "bathymetry_y": -0.2, "source H": 0.2, "source Hu": 0.4, "source Hv": -0.1},
+    "helmholtz": {"c2r_x": 1.3, "c2r_y": 0.8, "c2r_z": 1.9, "c2i_x": 0.4, "c2i_y": -0.6, "c2i_z": 0.25, "omega2r": 2.1,
+                  "omega2i": 0.3, "source_r": 2.0, "source_i": -1.5},
+    "cdr": {"source": 2.0, "specific heat": 1.4, "density": 1.3, "zvel": 0.4},
+    "navierstokes+cdr": dict(NS_NUMBERS, **{"source": 2.0, "specific heat": 1.4, "zvel": 0.4}),
+    "navierstokes+thermal": dict(NS_NUMBERS, **{"thermal source": 3.0, "thermal diffusion": 1.7, "specific heat": 1.4, "beta": 0.7,
+                                                "T_ambient": 0.3, "include advection": 1, "bx": 0.8, "by": -0.5, "bz": 0.3}),
+    "linearelasticity+thermal": {"lambda": 1.1, "mu": 0.6, "source dx": 0.3, "source dy": 0.7, "source dz": -0.2, "thermal source": 3.0,
+                                 "thermal diffusion": 1.7, "specific heat": 1.4, "density": 1.3, "incplanestress": 1, "alpha_T": 0.35,
+                                 "T_ambient": 0.3, "include advection": 1, "bx": 0.8, "by": -0.5, "bz": 0.3},
+}
+SWITCHES = ("usePSPG", "useLSIC", "useSUPG", "transient", "incplanestress", "include advection")
+
+
+class _PointOnMpf:
+    """One point's coordinates as mpf under the indexing the point functions use: x.shape[2], x[..., d]."""
+
+    def __init__(self, v):
+        self.v, self.shape = v, (1, 1, len(v))
+
+    def __getitem__(self, idx):
+        return self.v[idx[-1]]
+
+
+@pytest.mark.parametrize("module,dim", [(m, d) for m in H.LATER for d in (2, 3) if (m, d) != ("shallowwater", 3)])   # (a 2-D module)
+def test_complex_step_matches_mpmath_diff_of_the_later_point_functions(module, dim):
+    """C = dF/dU and dF/dUdot of every later module's point function by the complex step in clongdouble against mpmath.diff
+    of the same expressions on mpf (the point functions are plain arithmetic: they run on mpf as they stand), at one point
+    with every term switched on; cdr with the deck strings that read c, c_t, grad(c)[x] and ux."""
+    S = 1 + dim
+    nv = {"stokes": dim + 1, "shallowwater": 3, "helmholtz": 2, "cdr": 1, "linearelasticity+thermal": dim + 1}.get(module, dim + 2)
+    K = nv * S
+    rng = np.random.default_rng(17)
+    U0, Ud0 = rng.uniform(-1, 1, K), rng.uniform(-1, 1, K)
+    if module == "shallowwater":
+        U0[0] = 0.8                                             # a depth xi + b well above 0
+    x = np.array([0.25, 0.4, 0.15], LD)[:dim].reshape(1, 1, dim)
+    P = dict(POINT_PARAMS[module])
+    if "cdr" in module:
+        P.update(_fields_of_c(module))
+    U, Ud = U0.astype(LD).reshape(K, 1, 1), Ud0.astype(LD).reshape(K, 1, 1)
+    F, CU, CT = H.point_derivative(H.POINT[module], U, Ud, x, dict(P, h=np.full((1, 1), LD(0.37))))
+
+    with mpmath.workdps(40):
+        Pm = {k: (mpmath.mpf(v) if isinstance(v, float) and k not in SWITCHES else v) for k, v in P.items()}
+        Pm["h"] = mpmath.mpf(float(LD(0.37)))
+        Um, Udm = [mpmath.mpf(float(v)) for v in U0], [mpmath.mpf(float(v)) for v in Ud0]
+        xm = _PointOnMpf([mpmath.mpf(float(v)) for v in x[0, 0]])
+        F_mp = lambda Uv, Udv: H.POINT[module](Uv, Udv, xm, Pm)
+        Fm = F_mp(Um, Udm)
+        assert len(Fm) == F.shape[0]
+        scale = max(abs(f) for f in Fm)
+        nonzero = 0
+        for k in range(len(Fm)):
+            assert abs(H._ld(Fm[k] + mpmath.mpf(0)) - F[k, 0, 0]) < 1e-18 * float(scale), k
+            for l in range(K):
+                def f(t, k=k, l=l):
+                    return F_mp([u + (t if j == l else 0) for j, u in enumerate(Um)], Udm)[k] + mpmath.mpf(0)
+                ref = mpmath.diff(f, 0)
+                nonzero += ref != 0
+                assert abs(H._ld(ref) - CU[k, l, 0, 0]) < 1e-17 * max(1.0, float(abs(ref))), (k, l, float(ref), float(CU[k, l, 0, 0]))
+            for l in range(0, K, S):
+                def g(t, k=k, l=l):
+                    return F_mp(Um, [u + (t if j == l else 0) for j, u in enumerate(Udm)])[k] + mpmath.mpf(0)
+                ref = mpmath.diff(g, 0)
+                assert abs(H._ld(ref) - CT[k, l, 0, 0]) < 1e-17 * max(1.0, float(abs(ref))), (k, l)
+        assert nonzero >= K                                     # (the comparison is not one of zeros)
+
+
 def test_a_wrong_dof_ordering_is_a_gross_failure(oracle):
     c = H.build_case(oracle, "thermal", H.SHAPES["thermal"][1], "unit", False)
     m = dict(c["m"])
@@ -163,12 +244,31 @@ def oracle_arrays(oracle, c):
         out = oracle.assemble_block(m, oracle.PHYS_NAVIERSTOKES, c["qdeg"], c["u"], funcs=funcs,
                                     params=[P["useSUPG"], P["usePSPG"], P["fix_uz_offsets"]], fixed=c["fixed"], transient=tr,
                                     want_local=True, rowptr=g["rowptr"], colind=g["colind"])
-    else:
+    elif mod == "linearelasticity":
         import linearelasticity_ref as R
         funcs = {k: P[k] for k in ("lambda", "mu", "source dx", "source dy", "source dz")}
         out = R.assemble(oracle, m, c["qdeg"], c["u"], funcs=funcs, params=dict(incplanestress=P["incplanestress"]),
                          fixed=c["fixed"], transient=tr, rowptr=g["rowptr"], colind=g["colind"])
+    else:
+        out = later_oracle_arrays(oracle, c)
     return out
+
+
+def later_oracle_arrays(oracle, c, **over):
+    """The float64 restatements of the later point-engine modules (tests/*_ref.py on oracle_lib's tables) on the case's
+    inputs.  over: functions / parameters to replace (the sensitivity test takes one term out with them)."""
+    import importlib
+    m, tr, mod, g = c["m"], c["tr"], c["module"], c["g"]
+    funcs, params = H.deck(dict(c, P=dict(c["P"], **over)))
+    R = importlib.import_module({"cdr": "cdr_ref", "navierstokes+cdr": "cdr_ref", "helmholtz": "helmholtz_ref", "stokes": "stokes_ref",
+                                 "shallowwater": "shallowwater_ref", "navierstokes+thermal": "ns_thermal_ref",
+                                 "linearelasticity+thermal": "thermoelastic_ref"}[mod])
+    kw = dict(funcs=funcs, fixed=c["fixed"], transient=tr, rowptr=g["rowptr"], colind=g["colind"])
+    if mod in ("stokes", "navierstokes+thermal", "linearelasticity+thermal"):
+        kw["params"] = params
+    if mod == "navierstokes+cdr":
+        kw["ns_params"] = [params[k] for k in ("useSUPG", "usePSPG", "fix_uz_offsets")]
+    return R.assemble(oracle, m, c["qdeg"], c["u"], **kw)
 
 
 def distances(c, got):
@@ -189,18 +289,62 @@ def test_oracle_against_the_yardstick(oracle, module, family):
     """Every entry of the oracle's element arrays, CRS values and residual, every shape, steady and at stage 1.  This is
     the first pin of the oracle's Q2-hex thermal and 3-D Q2/Q1 navierstokes element arrays beyond 6 digits."""
     K = 0.0
-    for shape in H.SHAPES[module]:
-        for transient in H.transients(module, family):
-            c = H.build_case(oracle, module, shape, family, transient)
-            assert np.array_equal(c["g"]["colind"], oracle.build_graph(c["m"]["ndof"], c["m"]["lids"])[1])
-            d = distances(c, oracle_arrays(oracle, c))
-            print("%-16s %-18s %-10s %-9s " % (module, family, shape[0], "stage 1" if transient else "steady") +
-                  "  ".join("%s %.3g" % kv for kv in d.items()))
-            assert all(v == v for v in d.values()), d
-            K = max(K, max(d.values()))
+    for shape, transient, variant in H.case_list(module, family):
+        c = H.build_case(oracle, module, shape, family, transient, variant)
+        assert np.array_equal(c["g"]["colind"], oracle.build_graph(c["m"]["ndof"], c["m"]["lids"])[1])
+        if module in H.LATER:
+            share = c["fixed"].mean()
+            assert 0.10 <= share <= 0.30, ("the strong rows' share of all rows", c["tag"], share)
+        d = distances(c, oracle_arrays(oracle, c))
+        print("%-16s %-18s %-40s " % (module, family, c["tag"]) + "  ".join("%s %.3g" % kv for kv in d.items()))
+        assert all(v == v for v in d.values()), d
+        K = max(K, max(d.values()))
     rec = H.K_ORACLE.get((module, family))
     print("K_oracle[%s, %s] = %.4g (recorded %s, device bound %s)" %
           (module, family, K, rec, H.device_bound(module, family) if rec is not None else None))
     assert rec is not None, "no recorded K_oracle"
     assert K <= rec, "the oracle is farther from the yardstick than recorded"
     assert rec <= 1.5 * K + 1.0, "the recorded K_oracle is stale (more than half above the measurement)"
+
+
+# ---- the bound is not slack: one term of a restatement off by a relative 2^-40 ----------------------------------------------
+def _without(oracle, c, **over):
+    return later_oracle_arrays(oracle, c, **over)
+
+
+def _term(full, less):
+    return {k: full[k] - less[k] for k in ("crs_vals", "res", "local_J", "local_res") if k in full}
+
+
+def _buoyancy_pspg_part(oracle, c, full):
+    """[PSPG on - off] with beta minus the same without: the undivided buoyancy part of the PSPG rows alone."""
+    on0, off, off0 = _without(oracle, c, beta=0.0), _without(oracle, c, usePSPG=0), _without(oracle, c, usePSPG=0, beta=0.0)
+    return {k: (full[k] - off[k]) - (on0[k] - off0[k]) for k in ("crs_vals", "res", "local_J", "local_res")}
+
+
+ONE_TERM = {   # module -> (variant, what the term is, its contribution to the restatement's arrays)
+    "stokes": (3, "the LSIC contribution", lambda o, c, full: _term(full, _without(o, c, useLSIC=0))),
+    "shallowwater": (0, "g xi b_x", lambda o, c, full: _term(full, _without(o, c, bathymetry_x=0.0))),
+    "helmholtz": (0, "the c2i_y direction", lambda o, c, full: _term(full, _without(o, c, c2i_y=0.0))),
+    "cdr": (0, "xvel c_x", lambda o, c, full: _term(full, _without(o, c, xvel=0.0))),
+    "navierstokes+cdr": (0, "xvel c_x", lambda o, c, full: _term(full, _without(o, c, xvel=0.0))),
+    "navierstokes+thermal": (0, "the buoyancy part of PSPG", _buoyancy_pspg_part),
+    "linearelasticity+thermal": (0, "alpha_T (e - T_ambient) in the normal stresses", lambda o, c, full: _term(full, _without(o, c, alpha_T=0.0))),
+}
+
+
+@pytest.mark.parametrize("module", H.LATER)
+def test_one_term_off_by_2_to_the_minus_40_exceeds_the_device_bound(oracle, module):
+    """ONE term of the float64 restatement's output, on the unit family, perturbed by a relative 2^-40 (8192 units of
+    2^-53): the distance from the yardstick must exceed device_bound -- a device with that error in that term fails."""
+    variant, what, term = ONE_TERM[module]
+    bound = H.device_bound(module, "unit")
+    for transient in (False, True):
+        c = H.build_case(oracle, module, H.SHAPES[module][0], "unit", transient, variant)
+        full = later_oracle_arrays(oracle, c)
+        t = term(oracle, c, full)
+        assert max(np.abs(v).max() for v in t.values()) > 0, what
+        clean, off = distances(c, full), distances(c, {k: full[k] + 2.0 ** -40 * t[k] for k in t})
+        print("%-26s %-48s %-8s d %.3g -> %.3g  (bound %.3g)" % (module, what, "stage 1" if transient else "steady",
+                                                                   max(clean.values()), max(off.values()), bound))
+        assert max(clean.values()) <= bound < max(off.values()), (what, clean, off, bound)
